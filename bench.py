@@ -11,7 +11,12 @@ Multi-GPU (torchrun, one process per GPU): frames shard with no data-path
 collective; rank r decodes frames [r*F, (r+1)*F) of the seed stream (weak
 scaling) and the counters are summed with one all-reduce per step.
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints ONE short JSON line
+on rank 0 (the headline figure, ms_per_step and the counters' statistics).
+--dump-outputs DIR also writes what the last timed step returned as DIR/*.npy.
+--full adds every side measurement to the line: the roofline block, end to end,
+the binary32 variants, the config-3 sweep, config 4 and the CPU baseline (each
+with its own --no-* switch).
 """
 from __future__ import annotations
 
@@ -61,6 +66,12 @@ def parse():
     ap.add_argument("--max-iters", type=int, default=50)
     ap.add_argument("--threshold", type=float, default=100.0)
     ap.add_argument("--seed", type=int, default=777)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (roofline block, end to end, binary32 variants, "
+                         "config-3 sweep, config 4, CPU baseline); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (iterations, syndromes_match, keys_match "
+                         "per frame of rank 0's shard, and the counters record) as DIR/<name>.npy")
     ap.add_argument("--cpu-frames", type=int, default=8192,
                     help="frames in the CPU-baseline sample (0 disables)")
     ap.add_argument("--cpu-threads", type=int, default=16,
@@ -76,8 +87,8 @@ def parse():
     ap.add_argument("--no-sweeps", action="store_true",
                     help="skip the config-3 QBER sweep (and config 4, as --config4-frames 0)")
     ap.add_argument("--config4-frames", type=int, default=None,
-                    help="frames of the configs[3] run sharded over the ranks (default 1,000,000, "
-                         "0 with --no-sweeps; 0 disables)")
+                    help="frames of the configs[3] run sharded over the ranks (--full only: default "
+                         "1,000,000, 0 with --no-sweeps; 0 disables)")
     ap.add_argument("--phase-timing", action="store_true",
                     help="per-phase shader-clock shares of the decoder (diagnostic; the QKD_PHASE_TIMING "
                          "option)")
@@ -85,6 +96,10 @@ def parse():
                     help="a library debug / A-B option (qkd_debug_set_option, include/qkd_ldpc.h), "
                          "process-wide; repeatable. The library reads no environment variable")
     args = ap.parse_args()
+    if not args.full:
+        if args.config4_frames:
+            ap.error("--config4-frames needs --full")
+        args.no_e2e = args.no_variants = args.no_sweeps = args.no_cpu_baseline = True
     if args.config4_frames is None:
         args.config4_frames = 0 if args.no_sweeps else 1_000_000
     return args
@@ -246,6 +261,38 @@ def roofline_block(variant, alg_bytes, kernel_s, call_s, kernel_name):
         out["rocprof_warm_ms"] = warm
         out["rocprof_source"] = wsrc
     return out
+
+
+DUMP_MAX_FRAMES = 2 << 20      # 3 float32 arrays + a float64 index of this many frames: 40 MiB
+
+
+def dump_outputs(path, iters, sp, ko, counters, Q):
+    """--dump-outputs: what a caller of the timed path holds after its last step,
+    as path/<name>.npy: the per-frame outputs of qkd_qkd_ldpc_batch (iterations,
+    syndromes_match, keys_match; float32, exact for these small integers) and the
+    qkd_counters record of qkd_counters_batch, all-reduced over the ranks (float64:
+    frames, sp_ok, ldpc_ok, sum_iters, sum_iters_sq, min_iters, max_iters). The
+    inputs are a function of --seed, --frames and --qber alone, so two builds run
+    with the same arguments are comparable array for array. More than
+    DUMP_MAX_FRAMES frames are sampled (a fixed seeded choice, listed in
+    frame_index.npy)."""
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    c = Q.read_counters(counters)
+    arrays = {"iterations": iters.cpu().numpy(), "syndromes_match": sp.cpu().numpy(),
+              "keys_match": ko.cpu().numpy()}
+    F = arrays["iterations"].size
+    if F > DUMP_MAX_FRAMES:
+        pick = np.sort(np.random.default_rng(0).choice(F, DUMP_MAX_FRAMES, replace=False))
+        arrays = {k: v[pick] for k, v in arrays.items()}
+        arrays["frame_index"] = pick
+    arrays = {k: v.astype(np.float64 if k == "frame_index" else np.float32) for k, v in arrays.items()}
+    arrays["counters"] = np.array([c.frames, c.sp_ok, c.ldpc_ok, c.sum_iters, c.sum_iters_sq,
+                                   c.min_iters, c.max_iters], np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def decoder_ms(L, ws, start):
@@ -570,35 +617,39 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before any later step touches the output buffers again
+        dumped = dump_outputs(args.dump_outputs, iters, sp, ko, counters, Q)
+    extra_steps = 0
     if args.kernel_events == "on":
         dec_ms = decoder_ms(L, ws, False)
-    else:
+    elif args.full:
         decoder_ms(L, ws, True)
         for k in range(3):
             step()
         dec_ms = decoder_ms(L, ws, False)
+        extra_steps += 3
+    else:
+        dec_ms = None
     # every rank's own time, barrier-inclusive time and decoder-kernel time in one
     # all-gather: the max is the job's time, the spread its load imbalance
     per_rank = rank_times([own_elapsed, elapsed, dec_ms or 0.0], world)
     elapsed = max(r[1] for r in per_rank)
-    # the whole library call (pack, frame syndromes, decoder), HIP events around it,
-    # in a short untimed pass after the timed region
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(5)]
-    for k in range(5):
-        step(evs[k])
-    torch.cuda.synchronize()
-    kernel_ms = [a.elapsed_time(b) for a, b in evs]
+    kernel_ms = None
+    if args.full:
+        # the whole library call (pack, frame syndromes, decoder), HIP events around it,
+        # in a short untimed pass after the timed region
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(5)]
+        for k in range(5):
+            step(evs[k])
+        torch.cuda.synchronize()
+        kernel_ms = [a.elapsed_time(b) for a, b in evs]
+        extra_steps += 5
 
     c = Q.read_counters(counters)
-    it_np = iters.cpu().numpy()
     frames_total = F * world
     value = frames_total * N_BITS * args.steps / elapsed
-    # per-launch algorithmic bytes on this rank (executed iterations)
-    sum_it_local = int(it_np.astype(np.int64).sum())
-    b_iter = B_ITER if args.variant == "sp_f64" else B_ITER32
-    alg_bytes = sum_it_local * b_iter + F * B_FRAME
-    avg_call_s = float(np.mean(kernel_ms)) / 1e3
-    avg_kernel_s = dec_ms / 1e3
     replays = Q.spec_replays(ws, reset=True)
 
     stats = Q.counters_to_stats(c, frames_total, args.max_iters, q)
@@ -630,17 +681,25 @@ def main():
             "fer": stats["fer"],
             "mean_iterations": stats["iterations_successful_sp_mean"],
             "sum_iterations": stats["sum_iters_sp"],
-            "roofline": roofline_block(
-                args.variant, alg_bytes, avg_kernel_s, avg_call_s,
-                "decode_split_kernel (HIP events around its launch on its stream); call = "
-                "qkd_qkd_ldpc_batch: pack + frame syndromes + decoder (key compare in its epilogue)"),
+            "decoder_kernel_ms": dec_ms,
             "speculation": {
                 "replayed_frames": replays,
-                "frames": F * (prewarm_steps + args.warmup + args.steps + 5 + (3 if args.kernel_events == "off" else 0)),
+                "frames": F * (prewarm_steps + args.warmup + args.steps + extra_steps),
                 "note": "frames whose interval iterations could not certify every hard "
                         "decision, decoded again exactly (outputs bit-exact either way)",
             },
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if args.full:
+            # per-launch algorithmic bytes on this rank (executed iterations)
+            sum_it_local = int(iters.cpu().numpy().astype(np.int64).sum())
+            b_iter = B_ITER if args.variant == "sp_f64" else B_ITER32
+            alg_bytes = sum_it_local * b_iter + F * B_FRAME
+            out["roofline"] = roofline_block(
+                args.variant, alg_bytes, dec_ms / 1e3, float(np.mean(kernel_ms)) / 1e3,
+                "decode_split_kernel (HIP events around its launch on its stream); call = "
+                "qkd_qkd_ldpc_batch: pack + frame syndromes + decoder (key compare in its epilogue)")
         if world > 1:
             out["per_rank"] = {
                 "step_ms": [r[0] * 1e3 / args.steps for r in per_rank],

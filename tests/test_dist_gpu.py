@@ -60,7 +60,7 @@ def test_bench_config4_over_two_ranks():
     env["QKD_DIST_BACKEND"] = "gloo"
     frames = 20000
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1",
-                        "--warmup", "0", "--prewarm-ms", "0", "--frames", "256", "--no-e2e", "--no-variants",
+                        "--warmup", "0", "--prewarm-ms", "0", "--frames", "256", "--full", "--no-e2e", "--no-variants",
                         "--no-cpu-baseline", "--config4-frames", str(frames)],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]

@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.conftest import REF_ROOT
+from tests.conftest import GOLDEN
 
 
 def test_seeds_match_reference(probe, oracle_mod):
@@ -94,9 +94,9 @@ def test_golden_vectors_regenerate(golden_vectors, oracle_code, oracle_mod):
 
 
 def test_golden_code_matches_reference_file(golden_code, oracle_mod):
-    path = os.path.join(REF_ROOT, "alist_sparse_matrices", "(N=10240,M=5231,R=0.49,CW=3,SEED=666).txt")
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
+    """tests/golden/alist_n10240.txt is the reference's matrix file
+    alist_sparse_matrices/(N=10240,M=5231,R=0.49,CW=3,SEED=666).txt, byte for byte."""
+    path = os.path.join(GOLDEN, "alist_n10240.txt")
     code = oracle_mod.Code.from_alist(path)
     bo, bi, co, ci = code.lists()
     assert (bo == golden_code["bit_off"]).all() and (bi == golden_code["bit_idx"]).all()

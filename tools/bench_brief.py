@@ -1,4 +1,4 @@
-"""One-screen summary of a bench.py JSON line: python tools/bench_brief.py FILE"""
+"""One-screen summary of a `bench.py --full` JSON line: python tools/bench_brief.py FILE"""
 import json
 import sys
 

@@ -22,7 +22,7 @@ for l in $LIBS; do
 done
 for r in $(seq $REPS); do
   for l in $LIBS; do
-    QKD_AMD_DIAGNOSTIC=1 QKD_AMD_LIB=$(libpath $l) timeout -k 10 120 python bench.py --no-cpu-baseline --no-variants \
+    QKD_AMD_DIAGNOSTIC=1 QKD_AMD_LIB=$(libpath $l) timeout -k 10 120 python bench.py --full --no-cpu-baseline --no-variants \
       --no-sweeps --steps 20 $(libopt $l) ${BENCH_EXTRA:-} > $O/bench_$l.json 2> $O/bench_$l.err || { tail $O/bench_$l.err; exit 1; }
     python -c "
 import json;d=json.loads(open('$O/bench_$l.json').read().strip().splitlines()[-1])
@@ -52,7 +52,7 @@ fi
 if [ -n "${TRACE:-}" ]; then
   for l in $LIBS; do
     QKD_AMD_DIAGNOSTIC=1 QKD_AMD_LIB=$(libpath $l) timeout -k 10 300 rocprofv3 --kernel-trace \
-      --output-format csv -d $O/trace_$l -o run -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline \
+      --output-format csv -d $O/trace_$l -o run -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline \
       --no-variants --no-sweeps $(libopt $l) > $O/trace_$l.log 2>&1 || { echo "trace $l failed"; tail $O/trace_$l.log; exit 1; }
     f=$(find $O/trace_$l -name "run_kernel_trace.csv" | head -1)
     python3 tools/prof_summary.py "$(dirname $f)" $O/trace_$l.json && python3 - $O/trace_$l.json $l <<'PY'

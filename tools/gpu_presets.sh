@@ -53,7 +53,7 @@ e2e_timeline)
   python3 tools/e2e_timeline.py --summarise $O/p/run_kernel_trace.csv ;;
 variants)
   for v in ${@:-minsum sp_f32}; do
-    timeout -k 10 120 python bench.py --variant $v --phase-timing --no-cpu-baseline --no-variants --no-sweeps --no-e2e \
+    timeout -k 10 120 python bench.py --full --variant $v --phase-timing --no-cpu-baseline --no-variants --no-sweeps --no-e2e \
       --steps 10 > $O/phase_$v.json 2> $O/phase_$v.err || { tail $O/phase_$v.err; exit 1; }
     python3 -c "
 import json;d=json.loads(open('$O/phase_$v.json').read().strip().splitlines()[-1])
@@ -78,7 +78,7 @@ minsum)
   tail -3 $O/pytest.log
   [ $rc -eq 0 ] || { grep -B3 -A30 "Error\|FAILED\|assert" $O/pytest.log | head -60; exit $rc; }
   for v in minsum minsum_sc sp_f32; do
-    timeout -k 10 120 python bench.py --variant $v --no-cpu-baseline --no-variants --no-sweeps --no-e2e --steps 20 \
+    timeout -k 10 120 python bench.py --full --variant $v --no-cpu-baseline --no-variants --no-sweeps --no-e2e --steps 20 \
       > $O/bench_$v.json 2> $O/bench_$v.err || { tail $O/bench_$v.err; exit 1; }
     python3 -c "
 import json;d=json.loads(open('$O/bench_$v.json').read().strip().splitlines()[-1])

@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 VARIANTS=${VARIANTS:-"sp_f64 sp_f32 minsum minsum_sc"}
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
-  python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-sweeps > "$OUT/trace.log" 2>&1 \
+  python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-sweeps > "$OUT/trace.log" 2>&1 \
   || { tail -n 20 "$OUT/trace.log"; exit 3; }
 tail -n 1 "$OUT/trace.log"
 python3 tools/prof_summary.py "$OUT/trace" "$OUT/kernel_summary.json" || exit 4
