@@ -258,6 +258,12 @@ QKD_API qkd_status qkd_counters_merge(const qkd_counters *records, size_t n_reco
  *   QKD_BIT_ORDER identity|runs  (ws == NULL, read when a code is created)
  *                              the split decoder's internal bit order
  *   QKD_PHASE_TIMING 1         per-phase shader clocks (qkd_debug_phase_cycles)
+ *   QKD_CHECK_LANES 0|1|2      the speculative check phases of check degrees
+ *                              <= 6: 0 one edge per lane; 1 (default) one
+ *                              check per lane in whole rounds of tasks, the
+ *                              remaining checks edge per lane; 2 every check
+ *                              on a lane (A/B). Chosen per launch; outputs
+ *                              are the same
  * An unknown name fails with QKD_ERR_INVALID_ARG. Thread-safe. No reference
  * counterpart (the reference's CFG fields are the decode parameters). */
 QKD_API qkd_status qkd_debug_set_option(qkd_workspace *ws, const char *name, const char *value);
@@ -284,6 +290,13 @@ QKD_API qkd_status qkd_debug_decoder_timing(qkd_workspace *ws, int start, double
  * sets how many interval iterations a frame may run first (0: off; default 8).
  * Outputs never depend on it. No reference counterpart. */
 QKD_API qkd_status qkd_debug_spec_replays(qkd_workspace *ws, uint64_t *replays, int reset);
+/* The check-phase form the last split-decoder launch on `ws` ran with: *form
+ * is QKD_CHECK_LANES as applied (0 where the launch's kernel has no check-lane
+ * phases, whatever the option says; -1 before any launch), *lane_tasks the
+ * 64-check tasks it ran one check per lane, *edge_tasks the tasks of its
+ * edge-lane plan (the remainder's, or the whole plan's with form 0). Any
+ * pointer may be NULL. No reference counterpart. */
+QKD_API qkd_status qkd_debug_check_lanes(qkd_workspace *ws, int32_t *form, int32_t *lane_tasks, int32_t *edge_tasks);
 /* Trace of one frame, the reference's TRACE_SUM_PRODUCT / TRACE_SUM_PRODUCT_LLR
  * (qkd_ldpc_algorithm.cpp:212-330): decodes llr[N] / syndrome[M] (host arrays)
  * with the reference rule (QKD_VARIANT_SP_F64 only) and records, for every

@@ -40,7 +40,7 @@ __all__ = [
     "sum_product_decoding_irregular", "sum_product_decoding_regular", "qkd_ldpc",
     "QKD_LDPC_irregular", "QKD_LDPC_regular", "keygen", "run_trials", "make_seeds",
     "qber_range", "Workspace", "counters_to_stats", "decoder_flags", "trace_decode", "set_debug_option",
-    "spec_replays", "interactive_simulation",
+    "spec_replays", "check_lanes", "interactive_simulation",
 ]
 
 
@@ -245,6 +245,15 @@ def spec_replays(ws: Workspace, reset: bool = False) -> int:
     v = C.c_uint64(0)
     N.check(N.lib().qkd_debug_spec_replays(ws.handle, C.byref(v), int(reset)))
     return int(v.value)
+
+
+def check_lanes(ws: Workspace):
+    """(form, lane_tasks, edge_tasks) of the last split-decoder launch on `ws`
+    (qkd_debug_check_lanes): QKD_CHECK_LANES as applied, the tasks run one check
+    per lane and the tasks of the edge-lane plan; form -1 before any launch."""
+    v = [C.c_int32(0) for _ in range(3)]
+    N.check(N.lib().qkd_debug_check_lanes(ws.handle, *[C.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
 
 
 def calculate_syndrome(H: HMatrix, bits, stream=None):

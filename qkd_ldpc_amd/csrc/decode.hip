@@ -1565,9 +1565,14 @@ static hipError_t decoder_event_close(qkd_workspace* ws, hipStream_t stream, hip
 // encode_seg; built on a layout's first launch and kept with the code
 // esz 4 (the binary32 min-sum rules, every slot in LDS): the slot word is
 // the slot's LDS byte address itself (no kSlotLds tag, no global form)
-static qkd_status plan_for_layout(const qkd_code* c, const SplitLds& L, int dc, const uint2** out, int esz = 8) {
+// cl_form (binary64 slots): 0 the edge-lane plan alone; 1 / 2 followed by the
+// split / pure check-lane plan of the code (qkd_code::cl_host): its
+// remainder's edge-lane plan, then the check-lane words (qkd_decode.h
+// cl_rem_offset, cl_words_offset)
+static qkd_status plan_for_layout(const qkd_code* c, const SplitLds& L, int dc, const uint2** out, int esz = 8,
+                                  int cl_form = 0) {
     std::lock_guard<std::mutex> lock(c->plan_mu);
-    const auto key = std::make_pair(L.S, ((uint32_t)L.msg << 8) | (uint32_t)dc | (esz == 4 ? 0x80u : 0u));
+    const auto key = std::make_pair(L.S, ((uint32_t)cl_form << 28) | ((uint32_t)L.msg << 8) | (uint32_t)dc | (esz == 4 ? 0x80u : 0u));
     auto it = c->d_plan_enc.find(key);
     if (it == c->d_plan_enc.end()) {
         std::vector<uint2> enc(c->plan_slot_host);
@@ -1576,6 +1581,28 @@ static qkd_status plan_for_layout(const qkd_code* c, const SplitLds& L, int dc, 
             w.x = esz == 4 ? (uint32_t)L.msg + w.x * 4u : encode_slot(w.x, L.S, (uint32_t)L.msg, (uint32_t)sizeof(double));
             w.y = encode_seg(w.y & qkdp::kPlanChkMask, (w.y >> 20) & 63u, (w.y >> 26) + 1, (uint32_t)(k & 63),
                              (uint32_t)dc);
+        }
+        if (cl_form != 0) {
+            const qkd_code::ClHost& h = c->cl_host[cl_form - 1];
+            const size_t at = enc.size();
+            enc.insert(enc.end(), h.rem.begin(), h.rem.end());
+            for (size_t k = at; k < enc.size(); ++k) {
+                uint2& w = enc[k];
+                w.x = encode_slot(w.x, L.S, (uint32_t)L.msg, (uint32_t)sizeof(double));
+                w.y = encode_seg(w.y & qkdp::kPlanChkMask, (w.y >> 20) & 63u, (w.y >> 26) + 1, (uint32_t)(k & 63),
+                                 (uint32_t)dc);
+            }
+            // per task dc rows of slot words, then the row of check words
+            const size_t tasks = h.chk.size() / 64;
+            std::vector<uint32_t> words(tasks * (size_t)(dc + 1) * 64);
+            for (size_t t = 0; t < tasks; ++t) {
+                for (size_t k = 0; k < (size_t)dc * 64; ++k)
+                    words[t * (size_t)(dc + 1) * 64 + k] =
+                        encode_slot(h.slot[t * (size_t)dc * 64 + k], L.S, (uint32_t)L.msg, (uint32_t)sizeof(double));
+                for (size_t l = 0; l < 64; ++l) words[(t * (size_t)(dc + 1) + (size_t)dc) * 64 + l] = h.chk[t * 64 + l];
+            }
+            words.resize((words.size() + 1) & ~(size_t)1, 0u);
+            for (size_t k = 0; k < words.size(); k += 2) enc.push_back(make_uint2(words[k], words[k + 1]));
         }
         uint2* d = nullptr;
         if (hipMalloc(&d, enc.size() * sizeof(uint2)) != hipSuccess)
@@ -1699,9 +1726,30 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
             a.code = c->view_split();     // the internal bit order (host.cpp build_code)
             a.c2b = ws->c2b;
             a.plan_enc = nullptr;
+            a.cl_split = 0;
+            ws->last_cl_form = 0;
+            ws->last_cl_tasks = 0;
+            ws->last_cl_rem_tasks = c->n_tasks;
             if (rule == kRuleSp64 || msr) {
-                s = plan_for_layout(c, L, sdc, &a.plan_enc, esz);
+                // the speculative check phases one check per lane (the default
+                // where the kernel has them: buckets 4 and 6, not the checkpointed
+                // form). QKD_CHECK_LANES: 0 edge-lane, 1 check-lane with the
+                // edge-lane remainder, 2 every check on a lane
+                int cl_form = 0;
+                if (spec && !ckpt && !long_code && rule == kRuleSp64 && c->cl_dc == sdc) {
+                    cl_form = kCheckLanesDefault;
+                    if (const DbgOpt e = debug_option(ws, "QKD_CHECK_LANES")) cl_form = std::max(0, std::min(2, e.as_int()));
+                }
+                s = plan_for_layout(c, L, sdc, &a.plan_enc, esz, cl_form);
                 if (s != QKD_OK) return s;
+                a.cl_split = 0;
+                if (cl_form != 0) {
+                    const qkd_code::ClHost& h = c->cl_host[cl_form - 1];
+                    a.cl_split = 0x80000000u | (uint32_t)h.cl_tasks | ((uint32_t)h.rem_tasks << 16);
+                    ws->last_cl_form = cl_form;
+                    ws->last_cl_tasks = h.cl_tasks;
+                    ws->last_cl_rem_tasks = h.rem_tasks;
+                }
             }
             const size_t slots = (size_t)c->max_dv * c->n_pad;
             // elements of the message type, plus kC2bPad: the workgroups' regions
@@ -2669,6 +2717,14 @@ qkd_status qkd_debug_spec_replays(qkd_workspace* ws, uint64_t* replays, int rese
     char* p = reinterpret_cast<char*>(ws->counter) + 120;
     QKD_HIP(hipMemcpy(replays, p, 8, hipMemcpyDeviceToHost));
     if (reset) QKD_HIP(hipMemset(p, 0, 8));
+    return QKD_OK;
+}
+
+qkd_status qkd_debug_check_lanes(qkd_workspace* ws, int32_t* form, int32_t* lane_tasks, int32_t* edge_tasks) {
+    if (!ws) return set_error(QKD_ERR_INVALID_ARG, "null workspace");
+    if (form) *form = ws->last_cl_form;
+    if (lane_tasks) *lane_tasks = ws->last_cl_tasks;
+    if (edge_tasks) *edge_tasks = ws->last_cl_rem_tasks;
     return QKD_OK;
 }
 

@@ -828,6 +828,166 @@ __device__ __forceinline__ void spec_check_phase_paired(const uint2* __restrict_
     if (bad != 0 && lane == 0) atomicOr(round_word, 2u);
 }
 
+// The same check phases with one CHECK per lane (the check-lane plan,
+// qkd_plan.h CheckLanePlan; buckets 4 and 6): a lane loads its check's DC
+// slots, forms every extrinsic sum in registers as a prefix plus a suffix sum
+// and writes the DC messages back -- no row buffer, no cross-lane step, the
+// parity a popcount of in-register sign bits, and DC / 2 independent packed
+// phi evaluations in flight per lane (the rule of decode_ilv.hip's check
+// phase, parity-tested since the interleaved decoder).
+// Entries past the check's degree read and write the dummy column's slot and
+// count as exact zeros; lanes without a check (degree 0) are all dead.
+// PSI_IN: the slots hold the psi bounds of exact b2c (iteration 2 after the
+// folded first one, psi_of_exact: the sign in the low word, NaN = uncertain);
+// otherwise b2c intervals, bounded two edges per packed call (phi_bounds2).
+// Any edge order gives an enclosing interval: the sums of DC - 1 terms are
+// widened by (DC + 2) kSumRel relative and kRefSumAbs absolute, as the
+// edge-lane phases charge theirs.
+// Pipeline, sized by registers (a lane's DC slots are DC times an edge-lane
+// task's, and the kernel's long-lived values leave the phase about 80 VGPRs
+// before anything goes to scratch): two sets of plan words (DC slot words and
+// the check's word per lane, coalesced rows of the task) alternate, the next
+// task's loaded under this task's output bounds, so nothing is copied between
+// tasks; a task's slots are loaded
+// at its start, both halves, and the other waves of the SIMD cover the round
+// trip (slots loaded a task ahead as well cost 12 more registers: 36 VGPRs
+// of the kernel spilled).
+template <int DC, bool PSI_IN>
+__device__ __forceinline__ void spec_check_phase_lanes(const uint32_t* __restrict__ clp,
+                                                       const SplitStore<double>& ms, int n_tasks, float thr_dn,
+                                                       float thr_up, uint32_t* round_word, int wave, int lane) {
+    using qkds::f2;
+    static_assert(DC % 2 == 0 && DC <= 8, "check-lane buckets: pairs of entries, degree <= 8");
+    constexpr int NW = kDecodeBlock / 64;
+    constexpr int NP = DC + 1;                   // words per lane and task
+    constexpr int HP = DC / 2;                   // pairs of entries
+    int t = wave;
+    if (t >= n_tasks) return;
+    struct Words {
+        uint32_t s[DC];     // encoded slot words
+        uint32_t c;         // the check's word (qkdp::encode_chk)
+    };
+    const uint32_t vlane = (uint32_t)lane * 4u;
+    // (the plan has kPlanPadTasks dead tasks past n_tasks: loads ahead need no
+    // test. Plain loads off the task's scalar base: a buffer resource would be
+    // four more scalars held through the phase in a kernel that spills them)
+    auto load_words = [&](int tt, Words& w) {
+        const char* const base =
+            reinterpret_cast<const char*>(clp) + (size_t)__builtin_amdgcn_readfirstlane(tt * (NP * 64 * 4));
+#pragma unroll
+        for (int k = 0; k < DC; ++k) w.s[k] = *reinterpret_cast<const uint32_t*>(base + k * 256 + vlane);
+        w.c = *reinterpret_cast<const uint32_t*>(base + DC * 256 + vlane);
+    };
+    bool bad = false;       // a live entry that could not certify (a lane mask: scalar ors)
+    auto step = [&](const Words& w_t, Words& w_n) -> bool {
+        typedef __attribute__((address_space(3))) const uint32_t LdsU32;
+        SplitStore<double>::Raw x[DC];
+#pragma unroll
+        for (int k = 0; k < DC; ++k) x[k] = ms.ld_raw(w_t.s[k]);
+        const uint32_t sword = *reinterpret_cast<LdsU32*>((size_t)qkdp::chk_word_addr(w_t.c));
+        const int deg = (int)qkdp::chk_word_deg(w_t.c);
+        // psi bounds of |b2c| per entry (exact zeros for dead ones) and the signs
+        f2 ph[DC];
+        uint32_t negs = 0;
+#pragma unroll
+        for (int k = 0; k < DC; k += 2) {
+            const f2 b0 = qkds::unpack_iv(ms.pick(x[k])), b1 = qkds::unpack_iv(ms.pick(x[k + 1]));
+            const bool in0 = k < deg, in1 = k + 1 < deg;
+            bool n0, n1, ok0, ok1;
+            f2 r0, r1;
+            if constexpr (PSI_IN) {
+                n0 = b0.x < 0.0f;
+                n1 = b1.x < 0.0f;
+                ok0 = b0.x == b0.x;
+                ok1 = b1.x == b1.x;
+                r0 = neg_iv_if(n0, b0);
+                r1 = neg_iv_if(n1, b1);
+            } else {
+                n0 = b0.y < 0.0f;
+                n1 = b1.y < 0.0f;
+                const f2 a0 = neg_iv_if(n0, b0), a1 = neg_iv_if(n1, b1);
+                // certified: the interval excludes 0 by a margin (spec_check_phase_paired)
+                ok0 = a0.x > 1.0e-30f;
+                ok1 = a1.x > 1.0e-30f;
+                qkds::phi_bounds2(a0, a1, r0, r1);
+            }
+            bad |= (in0 && !ok0) || (in1 && !ok1);
+            negs |= (in0 && n0 ? 1u : 0u) << k;
+            negs |= (in1 && n1 ? 1u : 0u) << (k + 1);
+            ph[k] = (in0 && ok0) ? r0 : f2{0.0f, 0.0f};
+            ph[k + 1] = (in1 && ok1) ? r1 : f2{0.0f, 0.0f};
+            // (one pair at a time: the scheduler otherwise interleaves all DC / 2
+            // evaluations, and their temporaries push the kernel's long-lived
+            // values into scratch)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // the next task's plan words, in flight under the output bounds (their
+        // registers are not held through the input bounds)
+        __builtin_amdgcn_sched_barrier(0);
+        load_words(t + NW, w_n);
+        __builtin_amdgcn_sched_barrier(0);
+        // sigma of entry k = s_j ^ parity of the signs ^ its own
+        const uint32_t sp = ((sword >> qkdp::chk_word_bit(w_t.c)) + (uint32_t)__popc(negs)) & 1u;
+        // extrinsic sums by pairs: entry k of pair i sums the pair's other
+        // entry and the other pairs (a prefix and a suffix over the pair
+        // sums; every term >= 0, at most DC - 2 additions per sum)
+        f2 pp[HP], oth[HP];
+#pragma unroll
+        for (int i = 0; i < HP; ++i) pp[i] = ph[2 * i] + ph[2 * i + 1];
+        {
+            f2 pre = pp[0];
+            oth[0] = f2{0.0f, 0.0f};
+#pragma unroll
+            for (int i = 1; i < HP; ++i) {
+                oth[i] = pre;
+                pre = pre + pp[i];
+            }
+            f2 suf = pp[HP - 1];
+#pragma unroll
+            for (int i = HP - 2; i >= 0; --i) {
+                oth[i] = i == 0 ? suf : oth[i] + suf;
+                suf = suf + pp[i];
+            }
+        }
+        auto ext_of = [&](int k) -> f2 {
+            const f2 sum = oth[k >> 1] + ph[k ^ 1];
+            const float mg = __builtin_fmaf(sum.y, (float)(DC + 2) * qkds::kSumRel, qkds::kRefSumAbs);
+            f2 e = sum + f2{-mg, mg};
+            e.x = e.x > 0.0f ? e.x : 0.0f;
+            bad |= k < deg && !(e.y < qkds::kPsiSumMax);      // the reference's product would underflow
+            return e;
+        };
+        // the c2b bounds two entries per packed evaluation, descending, each
+        // stored as it is made: threshold_matrix (:246-249) on the magnitude,
+        // then the sign
+#pragma unroll
+        for (int k = DC - 1; k >= 1; k -= 2) {
+            const f2 e1 = ext_of(k);
+            const f2 e0 = ext_of(k - 1);
+            f2 m0, m1;
+            qkds::phi_bounds_out2(e0, e1, m0, m1);
+            m0.x = __builtin_amdgcn_fmed3f(m0.x, 0.0f, thr_dn);
+            m0.y = __builtin_amdgcn_fmed3f(m0.y, 0.0f, thr_up);
+            m1.x = __builtin_amdgcn_fmed3f(m1.x, 0.0f, thr_dn);
+            m1.y = __builtin_amdgcn_fmed3f(m1.y, 0.0f, thr_up);
+            const uint32_t s0 = (sp ^ (negs >> (k - 1))) & 1u;
+            const uint32_t s1 = (sp ^ (negs >> k)) & 1u;
+            ms.st_w(w_t.s[k - 1], qkds::pack_iv(neg_iv_if(s0 != 0u, m0)));
+            ms.st_w(w_t.s[k], qkds::pack_iv(neg_iv_if(s1 != 0u, m1)));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        t = __builtin_amdgcn_readfirstlane(t + NW);
+        return t < n_tasks;
+    };
+    Words wa, wb;
+    load_words(t, wa);
+    for (;;) {
+        if (!step(wa, wb)) break;
+        if (!step(wb, wa)) break;
+    }
+    if (fold64(__ballot(bad)) != 0 && lane == 0) atomicOr(round_word, 2u);
+}
+
 // The folded first iteration as a table (speculative kernel, QKD path): its
 // messages are +-C_d (first_check_phase), so a bit's exact total and the psi
 // bounds of its b2c (spec_bit_phase, FOLD) depend only on its degree pattern
@@ -1193,8 +1353,29 @@ __device__ __forceinline__ uint32_t region_of_block() {
 // keys-path kernel only (the frame-interleaved decoder's hand-offs): Bob's
 // bits of rounds 64 and up come from the frame's key words kept in LDS (the
 // ftab region, DecodeArgs::ftab_entries >= words) instead of bobmask.
+//
+// The kernel's DecodeArgs as it lies in the kernel-argument segment. Fields
+// that a frame needs once (its array pointers, the queue's) are read through
+// this pointer where they are used -- a scalar load there -- instead of
+// through `a`, whose fields the compiler loads once per kernel and holds (or
+// spills) through every phase of every frame. `opaque` keeps it from hoisting
+// those loads out of the frame loop again. This relies on DecodeArgs being
+// the kernel's ONLY parameter, passed by value: the segment then starts with
+// it, at offset 0 (sole_decode_args, asserted in the kernel).
+typedef const __attribute__((address_space(4))) DecodeArgs KernArgs;
+__device__ __forceinline__ KernArgs* kernel_args() {
+    KernArgs* p = (KernArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+template <class... A>
+constexpr bool sole_decode_args(void (*)(A...)) {
+    return sizeof...(A) == 1 && (std::is_same<A, DecodeArgs>::value && ...);
+}
 template <int MODE, int RULE, int DC, bool CLAMP, int SPEC, bool LONG = false>
 __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
+    static_assert(sole_decode_args(&decode_split_kernel<MODE, RULE, DC, CLAMP, SPEC, LONG>),
+                  "kernel_args(): DecodeArgs must be the only kernel parameter");
     static_assert(!LONG || (MODE == kModeKeys && RULE == kRuleSp64 && SPEC == 0), "long codes: exact keys path");
     using T = typename RuleMsg<RULE>::T;
     // QKD path: the first check phase folds into the first bit phase for both
@@ -1241,6 +1422,13 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
     // the all-LDS binary32 rule; the dummy column's slot in the same form
     const uint2* const plan = (RULE == kRuleSp64 || MSR) ? a.plan_enc : c.plan_slot;
     const uint32_t dummy_w = encode_slot((uint32_t)c.n, L.S, (uint32_t)L.msg, (uint32_t)sizeof(T));
+    // the speculative check phases one check per lane (DecodeArgs::cl_split;
+    // buckets 4 and 6, not the checkpointed form): the check-lane words and
+    // the remainder's edge-lane plan follow the whole plan in plan_enc
+    // (decoded from cl_split at each phase: a few scalar operations there
+    // instead of six more long-lived scalars in a kernel that spills them)
+    // (bucket 8 keeps the edge-lane phases: eight slots per lane spill 44 VGPRs)
+    constexpr bool CLANES = SPEC == 1 && !LONG && (DC == 4 || DC == 6);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1310,8 +1498,10 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
     PhaseClock pc(a.phase);
 
     // frames from the queue: each frame's successor is claimed when the frame
-    // starts (thread 0 keeps it in a register until the frame's end), so the
-    // atomic's round trip overlaps the prologue's loads
+    // starts, so the atomic's round trip overlaps the prologue's loads. Thread 0
+    // holds it in a register through the prologue only: the successor, its
+    // policy window's word and this frame's replay events wait in ctl[8..11]
+    // for the frame's end (four VGPRs that every phase would otherwise carry).
     // the in-launch replay policy for frame fr (SPEC kernels; DecodeArgs::win):
     // whether window fr / W - win_lag replayed at most a sixth of its frames,
     // waiting (thread 0, between frames) until that window has completed. A
@@ -1323,56 +1513,78 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
     // needed: at agent scope those compile to a write-back (buffer_wbl2) and
     // an invalidation (buffer_inv) of the whole L2, which the frame loop can
     // not afford (measured +21 % per config-2 batch).
-    unsigned long long* const win64 = reinterpret_cast<unsigned long long*>(a.win);
+    // (thread 0, once or twice per frame: the windows' fields through the
+    // caller's kernel_args() as well)
+    auto win64 = [](KernArgs* ka) { return reinterpret_cast<unsigned long long*>(ka->win); };
     // window_of(fr): the window frame fr's policy reads, or -1 (none: always on)
-    auto window_of = [&](uint32_t fr) -> int {
-        if (!SPEC || a.spec_always || fr >= a.n_frames) return -1;
-        const uint32_t wn = fr >> a.win_shift;
-        return wn < a.win_lag ? -1 : (int)(wn - a.win_lag);
+    auto window_of = [&](KernArgs* ka, uint32_t fr) -> int {
+        if (!SPEC || ka->spec_always || fr >= ka->n_frames) return -1;
+        const uint32_t wn = fr >> ka->win_shift;
+        return wn < ka->win_lag ? -1 : (int)(wn - ka->win_lag);
     };
     // v: that window's word as read earlier (the frame's start, so the load's
     // latency overlaps the frame; almost always complete by then), polled again
     // only while incomplete
-    auto spec_policy = [&](uint32_t fr, unsigned long long v) -> uint32_t {
-        const int k = window_of(fr);
+    auto spec_policy = [&](KernArgs* ka, uint32_t fr, unsigned long long v) -> uint32_t {
+        const int k = window_of(ka, fr);
         if (k < 0) return 1u;
-        const uint32_t W = 1u << a.win_shift;
+        const uint32_t W = 1u << ka->win_shift;
         // (bounded, ~1 s: a defensive exit, never expected to be reached)
         for (uint32_t polls = 0; (uint32_t)v < W; ++polls) {
             if (polls >= (1u << 24)) return 1u;
             __builtin_amdgcn_s_sleep(2);
-            v = __hip_atomic_load(win64 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            v = __hip_atomic_load(win64(ka) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         return (uint32_t)(v >> 32) * 6u <= W ? 1u : 0u;     // kSpecReplayMax
     };
-    auto window_peek = [&](uint32_t fr) -> unsigned long long {
-        const int k = window_of(fr);
-        return k < 0 ? 0ull : __hip_atomic_load(win64 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    auto window_peek = [&](KernArgs* ka, uint32_t fr) -> unsigned long long {
+        const int k = window_of(ka, fr);
+        return k < 0 ? 0ull : __hip_atomic_load(win64(ka) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     };
     // the next frame of the queue: frame k, or with a frame list (the
     // interleaved decoder's hand-offs, decode_ilv.hip) its k-th entry
-    auto claim = [&]() -> uint32_t {
-        const uint32_t k = atomicAdd(a.counter, 1u);
-        if (a.frame_list == nullptr) return k;
-        return k < *a.frame_count ? a.frame_list[k] : a.n_frames;
+    // (thread 0, once per frame: the queue's pointers through the caller's
+    // kernel_args(), made in uniform control flow)
+    auto claim = [&](KernArgs* ka) -> uint32_t {
+        const uint32_t k = atomicAdd(ka->counter, 1u);
+        if (ka->frame_list == nullptr) return k;
+        return k < *ka->frame_count ? ka->frame_list[k] : ka->n_frames;
     };
+    KernArgs* const qa = kernel_args();
     if (tid == 0) {
-        ctl[1] = claim();
-        ctl[6] = spec_policy(ctl[1], window_peek(ctl[1]));
+        ctl[1] = claim(qa);
+        ctl[6] = spec_policy(qa, ctl[1], window_peek(qa, ctl[1]));
     }
-    uint32_t next_f = 0;
     for (;;) {
         pc.mark(4);
-        for (int w = tid; w < m_words; w += kDecodeBlock) {
+        // The thread's index as the frame's prologue and epilogue see it:
+        // opaque to the compiler, so the dozen per-thread addresses they form
+        // from it are made per frame (an add or a shift each) instead of once
+        // per kernel and held through every phase of every frame -- with one
+        // check per lane in the check phases those long-lived VGPRs were the
+        // ones that went to scratch (18 of them).
+        auto frame_tid = [&]() -> int {
+            int t0 = tid;
+            asm volatile("" : "+v"(t0));
+            return t0;
+        };
+        const int ptid = frame_tid();
+        // The frame's input and output arrays likewise: kernel_args() per
+        // frame, scalar loads in the prologue and the epilogue instead of
+        // SGPRs held (and spilled to VGPR lanes, read back in the bit phase's
+        // loops) through the frame's iterations.
+        KernArgs* const pa = kernel_args();
+        for (int w = ptid; w < m_words; w += kDecodeBlock) {
             xsyn[w] = 0;
             xunc[w] = 0;
         }
         __syncthreads();
         const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)ctl[1]);   // (uniform to the compiler)
-        if (f >= a.n_frames) break;
-        if (tid == 0) next_f = claim();
-        // this frame's replay events (thread 0; the policy's window count)
-        uint32_t frame_replays = 0;
+        if (f >= pa->n_frames) break;
+        uint32_t next_f = 0;
+        if (tid == 0) next_f = claim(pa);
+        // this frame's replay events (thread 0; the policy's window count): ctl[9]
+        uint32_t* const frame_replays = ctl + 9;
 
         // ---- prologue. Keys path: the frame's Bob words, in the internal
         //      bit order (frame_syn_kernel permuted them), staged in LDS (the
@@ -1382,16 +1594,17 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
         if (MODE == kModeKeys) {
             uint64_t* w = reinterpret_cast<uint64_t*>(smem + L.tval);
             uint64_t* aw = reinterpret_cast<uint64_t*>(smem + L.aw);
-            const bool ka = a.key_ok != nullptr;
-            for (int q = tid; q < (int)a.words; q += kDecodeBlock) {
-                const uint64_t bv = a.bob_w[(size_t)f * a.words + q];
-                const uint64_t av = ka ? a.alice_w[(size_t)f * a.words + q] : 0ull;
+            const bool ka = pa->key_ok != nullptr;
+            const uint32_t words = pa->words;
+            for (int q = ptid; q < (int)words; q += kDecodeBlock) {
+                const uint64_t bv = pa->bob_w[(size_t)f * words + q];
+                const uint64_t av = ka ? pa->alice_w[(size_t)f * words + q] : 0ull;
                 w[q] = bv;
                 aw[q] = av;
                 if constexpr (MSC || LONG) bwl[q] = bv;
             }
-            const uint32_t* sy = a.synw + (size_t)f * 2 * m_words;
-            for (int q = tid; q < m_words; q += kDecodeBlock) {
+            const uint32_t* sy = pa->synw + (size_t)f * 2 * m_words;
+            for (int q = ptid; q < m_words; q += kDecodeBlock) {
                 tsyn[q] = sy[q];
                 qsyn[q] = sy[m_words + q];
             }
@@ -1404,11 +1617,20 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
         // (the speculative kernel's replay policy for this frame: ctl[6])
         const bool spec0 = SPEC == 1 && ctl[6] != 0;
         uint64_t bobmask = 0;
+        // (thread 0: the successor is here by now -- the staging loads above
+        // waited the atomic out; its policy window is read under the rest of
+        // the prologue and kept at the prologue's end)
+        unsigned long long next_win = 0;
+        if (tid == 0) {
+            ctl[8] = next_f;
+            *frame_replays = 0;
+            if (SPEC) next_win = window_peek(pa, next_f);
+        }
         // the first check phase's b2c = LLR_i in every slot (:188), as enclosing
         // intervals when speculating (the LLR path has no folded first iteration)
         auto init_slots = [&](bool as_interval) {
             int r = 0;
-            for (int i = tid; i < c.n; i += kDecodeBlock, ++r) {
+            for (int i = frame_tid(); i < c.n; i += kDecodeBlock, ++r) {
                 T l;
                 if (MODE == kModeLlr) {
                     l = (T)a.llr[(size_t)f * c.n + c.perm[i]];
@@ -1440,18 +1662,18 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
         // frame_syn's words, q_j = s_j ^ (H bob)_j ^ (deg_j & sign(log_p))
         if constexpr (kRunSyn) {
             const int zwords = (int)(n_pad >> 6);
-            for (int q = tid; q < zwords; q += kDecodeBlock)
-                zw[q] = (MODE == kModeKeys && q < (int)a.words) ? bw[q] : 0ull;
+            for (int q = ptid; q < zwords; q += kDecodeBlock)
+                zw[q] = (MODE == kModeKeys && q < (int)pa->words) ? bw[q] : 0ull;
             if (MODE == kModeKeys) {
-                for (int w = tid; w < m_words; w += kDecodeBlock)
-                    xsyn[w] = tsyn[w] ^ qsyn[w] ^ (lsign ? c.chk_odd[w] : 0u);
+                for (int w = ptid; w < m_words; w += kDecodeBlock)
+                    xsyn[w] = tsyn[w] ^ qsyn[w] ^ (lsign ? pa->code.chk_odd[w] : 0u);
             }
         }
         // ---- prologue, LLR path: target syndrome bits per check (tsyn), thread per check
         if (MODE == kModeLlr) {
             for (int j0 = wave * 64; j0 < c.m; j0 += kDecodeBlock) {
                 const int j = j0 + lane;
-                const int sj = j < c.m ? (a.syn[(size_t)f * c.m + j] != 0) : 0;
+                const int sj = j < c.m ? (pa->syn[(size_t)f * c.m + j] != 0) : 0;
                 const uint64_t sm = __ballot(sj);
                 if (lane == 0) {
                     tsyn[j0 >> 5] = (uint32_t)sm;
@@ -1459,13 +1681,9 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
                 }
             }
         }
+        if (SPEC && tid == 0) *reinterpret_cast<unsigned long long*>(ctl + 10) = next_win;
         __syncthreads();
         pc.mark(0);
-        // (thread 0: the next frame's policy window, read here, after the
-        // prologue has waited out next_f's atomic, so the load's latency
-        // overlaps this frame's iterations)
-        unsigned long long next_win = 0;
-        if (SPEC && tid == 0) next_win = window_peek(next_f);
 
         // ---- iterations (:212-330): interval iterations (qkd_spec.h) in the
         //      speculative launch, the reference's binary64 ones otherwise
@@ -1473,8 +1691,8 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
         // a frame the policy keeps off the speculation counts as replayed (so
         // the policy, once on, stays on, and the call's count reports it)
         if (SPEC == 1 && !spec && tid == 0) {
-            atomicAdd(a.replay_count, 1u);
-            frame_replays++;
+            atomicAdd(pa->replay_count, 1u);
+            ++*frame_replays;
         }
         bool done = false;
         uint32_t it = 0;
@@ -1505,13 +1723,42 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
             uint32_t* rw = ctl + 4 + (rnd & 1u);
             if (SPEC && spec) {
                 if constexpr (SPEC) {
-                    // (iteration 2 after the folded first one: the slots hold
-                    // the phi bounds of exact b2c, psi_of_exact)
-                    if (!folded && fold1 && it == 1) {
+                    // Check lanes (DecodeArgs::cl_split): the check-lane tasks,
+                    // then the edge-lane phase over the remainder's plan -- a
+                    // call of its own, so that the whole-plan calls keep the
+                    // compile-time operands they had with one plan.
+                    const bool psi_in = fold1 && it == 1;
+                    uint32_t cs = 0;
+                    if constexpr (CLANES) cs = a.cl_split;
+                    if (folded) {
+                        // (the first check phase is folded into the bit phase)
+                    } else if (CLANES && (cs >> 31) != 0) {
+                        if constexpr (CLANES) {
+                            const int r_tasks = (int)((cs >> 16) & 0x7fffu);
+                            const uint2* const rplan = plan + cl_rem_offset(n_tasks);
+                            const uint32_t* const cl_words =
+                                reinterpret_cast<const uint32_t*>(plan + cl_words_offset(n_tasks, r_tasks));
+                            const int cl_tasks = (int)(cs & 0xffffu);
+                            if (psi_in) {
+                                spec_check_phase_lanes<DC, true>(cl_words, ms, cl_tasks, a.thr_dn, a.thr_up, rw, wave,
+                                                                 lane);
+                                spec_check_phase_psi<DC>(rplan, tsyn, ms, row, wtab, r_tasks, n_pad, dummy_w,
+                                                         a.thr_dn, a.thr_up, rw, wave, lane);
+                            } else {
+                                spec_check_phase_lanes<DC, false>(cl_words, ms, cl_tasks, a.thr_dn, a.thr_up, rw, wave,
+                                                                  lane);
+                                spec_check_phase_paired<DC>(rplan, tsyn, ms, row, wtab, r_tasks, n_pad, dummy_w,
+                                                            a.thr_dn, a.thr_up, rw, wave, lane);
+                            }
+                            __syncthreads();
+                        }
+                    } else if (psi_in) {
+                        // (iteration 2 after the folded first one: the slots hold
+                        // the phi bounds of exact b2c, psi_of_exact)
                         spec_check_phase_psi<DC>(plan, tsyn, ms, row, wtab, n_tasks, n_pad, dummy_w,
                                                  a.thr_dn, a.thr_up, rw, wave, lane);
                         __syncthreads();
-                    } else if (!folded) {
+                    } else {
                         spec_check_phase_paired<DC>(plan, tsyn, ms, row, wtab, n_tasks, n_pad, dummy_w, a.thr_dn,
                                                     a.thr_up, rw, wave, lane);
                         __syncthreads();
@@ -1732,9 +1979,9 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
                     ms.st((uint32_t)c.n, (T)0);
                 }
                 if (tid == 0) {
-                    atomicAdd(a.replay_count, 1u);
-                    atomicAdd(a.spec_replays, 1ull);
-                    frame_replays++;
+                    atomicAdd(pa->replay_count, 1u);
+                    atomicAdd(pa->spec_replays, 1ull);
+                    ++*frame_replays;
                 }
                 continue;
             }
@@ -1757,9 +2004,9 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
                     ms.st((uint32_t)c.n, (T)0);    // (as above)
                 }
                 if (tid == 0) {
-                    atomicAdd(a.replay_count, 1u);
-                    atomicAdd(a.spec_replays, 1ull);
-                    frame_replays++;
+                    atomicAdd(pa->replay_count, 1u);
+                    atomicAdd(pa->spec_replays, 1ull);
+                    ++*frame_replays;
                 }
             } else if (CKPT && !spec && it >= 2 && it + 1 < a.max_it && unsat < ck_lim) {
                 // (exact round: iteration it - 1 left its b2c in the slots, and
@@ -1774,47 +2021,50 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
 
         // ---- outputs: SP_result and the last hard decision (keys path:
         //      packed, for key_match_kernel's arrays_equal, :433)
+        const int etid = frame_tid();
+        KernArgs* const ea = kernel_args();
         if (MODE == kModeKeys) {
             // keys_match = arrays_equal(alice, decoded) (:433, :96-106), fused
             // here: this thread's word of the last hard decision against Alice's
             // (block-wide OR through ctl[7], no static LDS: the dynamic
             // allocation may take the whole 160 KB)
-            if (a.key_ok) {
+            if (ea->key_ok) {
                 // (Alice's word read here rather than held in registers
                 // through the frame's iterations; both words in the internal
                 // bit order)
                 const uint64_t* aw = reinterpret_cast<const uint64_t*>(smem + L.aw);
                 bool mis = false;
-                if (tid < (int)a.words) {
-                    uint64_t d = zw[tid] ^ aw[tid];
-                    if ((tid + 1) * 64 > c.n) d &= (1ull << (c.n - tid * 64)) - 1ull;
+                if (etid < (int)ea->words) {
+                    uint64_t d = zw[etid] ^ aw[etid];
+                    if ((etid + 1) * 64 > c.n) d &= (1ull << (c.n - etid * 64)) - 1ull;
                     mis = d != 0;
                 }
                 if (__any(mis) && lane == 0) atomicOr(ctl + 7, 1u);
             }
             // the packed decision for bits_out, internal order
             // (zout_unpack_kernel puts the bits back in place)
-            if (a.bits_out)
-                for (int q = tid; q < (int)a.words; q += kDecodeBlock) a.zout[(size_t)f * a.words + q] = zw[q];
-        } else if (a.bits_out) {
-            for (int i = tid; i < c.n; i += kDecodeBlock)
-                a.bits_out[(size_t)f * c.n + c.perm[i]] = (uint8_t)((zw[i >> 6] >> (i & 63)) & 1u);
+            if (ea->bits_out)
+                for (int q = etid; q < (int)ea->words; q += kDecodeBlock) ea->zout[(size_t)f * ea->words + q] = zw[q];
+        } else if (ea->bits_out) {
+            for (int i = etid; i < c.n; i += kDecodeBlock)
+                ea->bits_out[(size_t)f * c.n + c.perm[i]] = (uint8_t)((zw[i >> 6] >> (i & 63)) & 1u);
         }
         if (tid == 0) {
-            a.iters[f] = done ? it + 1 : a.max_it;
-            a.sp_ok[f] = done ? 1 : 0;
-            ctl[1] = next_f;
+            ea->iters[f] = done ? it + 1 : a.max_it;
+            ea->sp_ok[f] = done ? 1 : 0;
+            const uint32_t nf = ctl[8];
+            ctl[1] = nf;
             if (SPEC) {
                 // this frame into its window (its completion and its replay
                 // events in one add), then the next frame's policy
-                __hip_atomic_fetch_add(win64 + (f >> a.win_shift), ((unsigned long long)frame_replays << 32) | 1ull,
+                __hip_atomic_fetch_add(win64(ea) + (f >> ea->win_shift), ((unsigned long long)*frame_replays << 32) | 1ull,
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ctl[6] = spec_policy(next_f, next_win);
+                ctl[6] = spec_policy(ea, nf, *reinterpret_cast<const unsigned long long*>(ctl + 10));
             }
         }
         __syncthreads();
-        if (MODE == kModeKeys && a.key_ok && tid == 0) {
-            a.key_ok[f] = ctl[7] ? 0 : 1;
+        if (MODE == kModeKeys && ea->key_ok && tid == 0) {
+            ea->key_ok[f] = ctl[7] ? 0 : 1;
             ctl[7] = 0;
         }
     }

@@ -36,7 +36,7 @@ static const char* const kDebugOptions[] = {
     "QKD_SPEC_CAP", "QKD_SPEC_CKPT", "QKD_CKPT_UNSAT", "QKD_SPEC_POLICY", "QKD_FOLD_TABLE",
     "QKD_DECODE_KERNEL", "QKD_MINSUM_STORE", "QKD_DECODE_GRID", "QKD_SPLIT_BUDGET", "QKD_C2B_PAD",
     "QKD_ILV", "QKD_ILV_GRID", "QKD_KEYGEN", "QKD_SYN_SLICED", "QKD_SYN_BYTES", "QKD_BIT_ORDER",
-    "QKD_PHASE_TIMING"};
+    "QKD_PHASE_TIMING", "QKD_CHECK_LANES"};
 static std::mutex g_dbg_mu;                            // guards g_dbg and every workspace's dbg
 static std::map<std::string, std::string> g_dbg;
 
@@ -477,6 +477,35 @@ static qkd_status build_code(qkd_code* c, int32_t n, int32_t m, const int32_t* c
         QKD_HIP(hipMalloc(&c->d_plan_slot, plan2.size() * sizeof(uint2)));
         QKD_HIP(hipMemcpy(c->d_plan_slot, plan2.data(), plan2.size() * sizeof(uint2), hipMemcpyHostToDevice));
         c->plan_slot_host = std::move(plan2);
+        // the speculative check phases' check-lane plans (qkd_plan.h), for
+        // the buckets that have the kernel (decode_split.hip
+        // spec_check_phase_lanes): slot-addressed like plan_slot
+        c->cl_dc = 0;
+        if (c->d_bit_code && max_dc <= 6) {
+            const int dc = max_dc <= 4 ? 4 : 6;
+            std::vector<int32_t> slot_of(e);
+            for (int32_t k = 0; k < e; ++k) slot_of[k] = krow[k] * c->n_pad + inv[cidx[k]];
+            for (int form = 0; form < 2; ++form) {
+                qkdp::CheckLanePlan cl;
+                if (!qkdp::build_check_lane_plan(n, m, cptr, cidx, krow.data(), dc, kDecodeBlock / 64, form == 1, cl))
+                    return set_error(QKD_ERR_UNSUPPORTED, "check-lane plan: check degree outside [1, %d]", dc);
+                qkd_code::ClHost& h = c->cl_host[form];
+                h.cl_tasks = cl.n_tasks;
+                h.rem_tasks = cl.rem.n_tasks;
+                h.slot.resize(cl.edge.size());
+                for (size_t k = 0; k < cl.edge.size(); ++k)
+                    h.slot[k] = cl.edge[k] < 0 ? (uint32_t)n : (uint32_t)slot_of[cl.edge[k]];
+                h.chk = cl.chkw;
+                h.rem.resize(cl.rem.word.size());
+                for (size_t k = 0; k < cl.rem.word.size(); ++k) {
+                    const uint32_t b = cl.rem.word[k] & qkdp::kPlanBitMask;
+                    h.rem[k] = make_uint2((cl.rem.word[k] >> 24) * (uint32_t)c->n_pad +
+                                              (b < (uint32_t)n ? (uint32_t)inv[b] : b),
+                                          cl.rem.seg[k]);
+                }
+            }
+            c->cl_dc = dc;
+        }
     }
     // Key-generation jump-ahead: chunk = draws per lane, a multiple of 64 so
     // every lane's Alice bits fill whole words.

@@ -128,6 +128,13 @@ struct DecodeArgs {
     // decode_split_kernel, binary64 rule: DeviceCode::plan_slot with the slot
     // field encoded for this launch's layout (encode_slot)
     const uint2* plan_enc;
+    // speculative kernel, buckets 4 and 6 (QKD_CHECK_LANES): bit 31 set = the
+    // interval check phases run one check per lane (spec_check_phase_lanes)
+    // over cl_tasks = bits 0-15 tasks of the check-lane plan, then the
+    // edge-lane phase over the rem_tasks = bits 16-30 tasks of the remainder
+    // plan; both follow the edge-lane plan in plan_enc (cl_plan_offsets). 0:
+    // the edge-lane phases over the whole plan
+    uint32_t cl_split;
     // decode_split_kernel, kModeKeys: per frame 2 * m_words syndrome words
     // from frame_syn_kernel (target s_A, then the first-product signs), and
     // the frame's last hard decision out as packed words (key_match_kernel
@@ -646,6 +653,22 @@ __host__ __device__ inline uint32_t encode_seg(uint32_t j, uint32_t start, uint3
     const uint32_t pc = p < dc - 1 ? p : dc - 1;
     const uint32_t wi = dc <= 8 ? deg * 8 + pc : dc <= 16 ? (deg - 1) * dc + pc : deg - 1;
     return (j & 31u) | (start << kSegStartShift) | (wi << kSegWiShift) | (((j >> 5) * 4u) << kSegWordShift);
+}
+
+// The check-lane plan (qkd_plan.h CheckLanePlan) encoded for a layout: per
+// task dc + 1 rows of 64 words, one per lane: rows k < dc the encoded slot
+// word (encode_slot) of the lane's check's k-th entry (the dummy column's past
+// its degree), row dc the check's word as the plan builder made it
+// (qkdp::encode_chk: syndrome word offset, bit, degree).
+// In DecodeArgs::plan_enc the remainder's edge-lane plan (rem_tasks +
+// kPlanPadTasks tasks) follows the n_tasks + kPlanPadTasks tasks of the whole
+// edge-lane plan, and the check-lane words follow the remainder.
+static_assert(qkdp::kChkWordShift == kSegWordShift, "check words address syndrome words as segment words do");
+__host__ __device__ inline size_t cl_rem_offset(int n_tasks) {      // in uint2 words
+    return (size_t)(n_tasks + qkdp::kPlanPadTasks) * 64;
+}
+__host__ __device__ inline size_t cl_words_offset(int n_tasks, int rem_tasks) {
+    return cl_rem_offset(n_tasks) + (size_t)(rem_tasks + qkdp::kPlanPadTasks) * 64;
 }
 
 using DecodeFn = void (*)(DecodeArgs);

@@ -25,7 +25,10 @@ constexpr int kDecodeBlock = QKD_DECODE_BLOCK;
 constexpr int kTab2MaxDv = 3;   // <= the bit phase's unrolled rows (decode.hip kDvUnroll)
 constexpr int kTab2MaxEntries = 2048;
 constexpr int kFoldTabMaxEntries = 1024;   // speculative fold table (decode_split.hip), 8 B each
-constexpr size_t kC2bPad = 64;             // split kernels: slots added to each workgroup's global region
+// speculative check phases (decode_split.hip), buckets 4 and 6: 1 one check per
+// lane with an edge-lane remainder, 0 one edge per lane (QKD_CHECK_LANES overrides)
+constexpr int kCheckLanesDefault = 1;
+constexpr size_t kC2bPad = 64;            // split kernels: slots added to each workgroup's global region
 // per-bit arrays of the split kernels (bit_code, bit_pat): rounds of padding
 // past the last round, >= the largest bit-phase load batch minus one
 constexpr int kBitPadRounds = 4;
@@ -153,6 +156,10 @@ struct qkd_workspace {
     size_t c2b_slots = 0;
     // dynamic frame queue counter (zeroed per launch)
     uint32_t* counter = nullptr;
+    // the check-phase form of the last split-decoder launch (decode.hip;
+    // qkd_debug_check_lanes): QKD_CHECK_LANES' value as applied, its check-lane
+    // tasks and the edge-lane tasks of its remainder; -1 before any launch
+    int last_cl_form = -1, last_cl_tasks = 0, last_cl_rem_tasks = 0;
     // packed alice / bob keys (uint64 words) for the fused paths
     uint64_t* alice_w = nullptr;
     uint64_t* bob_w = nullptr;
@@ -221,6 +228,21 @@ struct qkd_code {
     std::vector<uint2> plan_slot_host;
     mutable std::map<std::pair<uint32_t, uint32_t>, uint2*> d_plan_enc;
     mutable std::mutex plan_mu;
+    // the check-lane plan of the speculative check phases (qkd_plan.h
+    // CheckLanePlan; cl_dc = its bucket, 0: none -- check degree past 6 or no
+    // bit_code), slot-addressed on the host: [0] the split form (whole rounds
+    // of check-lane tasks plus an edge-lane remainder), [1] the pure form
+    // (every check on a lane; A/B runs). slot: (cl_tasks + pad) * cl_dc * 64
+    // slot indices (the dummy column's for dead entries); chk: the lanes'
+    // check words as the builder made them (qkdp::encode_chk; 0: none); rem:
+    // the remainder's plan in plan_slot_host's form
+    struct ClHost {
+        int32_t cl_tasks = 0, rem_tasks = 0;
+        std::vector<uint32_t> slot, chk;
+        std::vector<uint2> rem;
+    };
+    int32_t cl_dc = 0;
+    ClHost cl_host[2];
     int32_t n_pat = 0;                  // 0: too many degree patterns for the table
     std::vector<uint8_t> pat_deg;
     uint16_t* d_bit_pat = nullptr;

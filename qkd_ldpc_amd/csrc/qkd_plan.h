@@ -148,4 +148,103 @@ inline bool build_wave_plan(int32_t n, int32_t m, const int32_t* cptr, const int
     return true;
 }
 
+// ---- the check-lane plan ------------------------------------------------------
+// The speculative check phases of small check-degree buckets (dc = 4, 6)
+// run one CHECK per lane instead: task T, lane l holds check chk[T * 64 + l]
+// and its dc entries edge[(T * dc + k) * 64 + l], k < dc (k-major across the
+// lanes: each of a task's dc loads is coalesced). Entries k >= the check's
+// degree are dead (-1): the kernels point them at the dummy column's slot and
+// give them weight 0. Lanes without a check (the last task's tail and the
+// kPlanPadTasks pad tasks) have chk = -1 and every entry dead.
+//
+// Split rule (pure = false): the check-lane part takes whole rounds of
+// round_tasks wave tasks (one per wave of the workgroup), i.e. the first
+// floor(m / (64 * round_tasks)) * 64 * round_tasks checks in ascending order,
+// so every wave runs the same number of them; the remaining checks go into an
+// ordinary edge-lane plan (rem, build_wave_plan over that subset, its segment
+// words carrying the checks' indices in H), at most a few tasks. pure = true:
+// every check is check-lane, ceil(m / 64) tasks, rem empty.
+//
+// Edge order within a check: the check's own (bits ascending). Any order is
+// certified; placing the entries so that the lanes' k-th loads spread over
+// the LDS bank pairs measured nothing (profiles/r07_ab.txt) and is not done.
+//
+// The lane's check as one word, the form the kernels read (row dc of a task):
+//   bits 0-4    j & 31: the target bit's position in its syndrome word
+//   bits 5-8    the check's degree (0: a lane without a check)
+//   bits 19-31  (j >> 5) * 4: the byte offset of the check's syndrome word
+//               (the split kernels' syndrome words lead their LDS; M <= 65536)
+constexpr uint32_t kChkDegShift = 5, kChkWordShift = 19;
+constexpr uint32_t encode_chk(uint32_t j, uint32_t deg) {
+    return (j & 31u) | (deg << kChkDegShift) | (((j >> 5) * 4u) << kChkWordShift);
+}
+constexpr uint32_t chk_word_bit(uint32_t w) { return w & 31u; }
+constexpr uint32_t chk_word_deg(uint32_t w) { return (w >> kChkDegShift) & 15u; }
+constexpr uint32_t chk_word_addr(uint32_t w) { return w >> kChkWordShift; }
+
+struct CheckLanePlan {
+    int32_t dc = 0;                   // entries per check
+    int32_t n_tasks = 0;              // check-lane tasks; edge / chk hold n_tasks + kPlanPadTasks
+    std::vector<int32_t> edge;        // [(n_tasks + pad) * dc * 64] check-CSR edge, -1 dead
+    std::vector<int32_t> chk;         // [(n_tasks + pad) * 64] the lane's check, -1 none
+    std::vector<uint32_t> chkw;       // [(n_tasks + pad) * 64] its word (encode_chk), 0 none
+    std::vector<int32_t> rem_checks;  // the checks of the edge-lane remainder, ascending
+    WavePlan rem;                     // their plan; slot_of_edge indexed by H's check-CSR edge (-1: not there)
+};
+
+inline bool build_check_lane_plan(int32_t n, int32_t m, const int32_t* cptr, const int32_t* cidx,
+                                  const int32_t* krow, int dc, int round_tasks, bool pure, CheckLanePlan& p) {
+    // (the check word holds the degree in 4 bits and the word offset in 13)
+    if (dc < 1 || dc > 15 || m > 65536 || round_tasks < 1) return false;
+    for (int32_t j = 0; j < m; ++j) {
+        const int32_t d = cptr[j + 1] - cptr[j];
+        if (d < 1 || d > dc) return false;
+    }
+    p.dc = dc;
+    const int32_t per_round = 64 * round_tasks;
+    const int32_t m_cl = pure ? m : (m / per_round) * per_round;
+    p.n_tasks = (m_cl + 63) / 64;
+    const size_t tasks_pad = (size_t)p.n_tasks + kPlanPadTasks;
+    p.edge.assign(tasks_pad * dc * 64, -1);
+    p.chk.assign(tasks_pad * 64, -1);
+    p.chkw.assign(tasks_pad * 64, 0u);
+    for (int32_t t = 0; t < p.n_tasks; ++t) {
+        for (int l = 0; l < 64; ++l) {
+            const int32_t j = t * 64 + l;
+            if (j >= m_cl) break;
+            p.chk[(size_t)t * 64 + l] = j;
+            const int32_t d = cptr[j + 1] - cptr[j];
+            p.chkw[(size_t)t * 64 + l] = encode_chk((uint32_t)j, (uint32_t)d);
+            for (int k = 0; k < d; ++k) p.edge[((size_t)t * dc + k) * 64 + l] = cptr[j] + k;
+        }
+    }
+    // the remainder: an edge-lane plan over the sub-matrix of the left-over checks
+    p.rem_checks.clear();
+    for (int32_t j = m_cl; j < m; ++j) p.rem_checks.push_back(j);
+    const int32_t mr = (int32_t)p.rem_checks.size();
+    std::vector<int32_t> rptr(mr + 1, 0), ridx, rrow, redge;
+    for (int32_t q = 0; q < mr; ++q) {
+        const int32_t j = p.rem_checks[q];
+        for (int32_t e = cptr[j]; e < cptr[j + 1]; ++e) {
+            ridx.push_back(cidx[e]);
+            rrow.push_back(krow[e]);
+            redge.push_back(e);
+        }
+        rptr[q + 1] = (int32_t)ridx.size();
+    }
+    p.rem = WavePlan();
+    if (!build_wave_plan(n, mr, rptr.data(), ridx.data(), rrow.data(), p.rem)) return false;
+    // (check indices of H in the segment words and the chk array)
+    for (size_t s = 0; s < p.rem.chk.size(); ++s) {
+        const int32_t q = p.rem.chk[s];
+        if (q < 0) continue;
+        p.rem.chk[s] = p.rem_checks[q];
+        p.rem.seg[s] = (p.rem.seg[s] & ~kPlanChkMask) | (uint32_t)p.rem_checks[q];
+    }
+    std::vector<int32_t> soe(cptr[m], -1);
+    for (size_t r = 0; r < redge.size(); ++r) soe[redge[r]] = p.rem.slot_of_edge[r];
+    p.rem.slot_of_edge.swap(soe);
+    return true;
+}
+
 }  // namespace qkdp

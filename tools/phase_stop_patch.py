@@ -8,6 +8,9 @@ one too). For the keys path with the folded first iteration:
     1 (folded check, empty)  2 bit phase 0   3 syndrome test 0
     4 iteration-2 check      5 bit phase 1   6 syndrome test 1
     7 paired check           8 bit phase 2   9 syndrome test 2 ...
+With check lanes (QKD_CHECK_LANES 1, the default for buckets 4 and 6) a check
+boundary covers the check-lane tasks and the edge-lane remainder together; run
+the stops with QKD_CHECK_LANES 2 (no remainder) or 0 to attribute one form.
 A stopped frame leaves through the normal epilogue (its outputs are garbage;
 the PMC run checks nothing). The counters of build K minus those of build K-1
 are the work of boundary K's phase over the frames that reach it (frames that
