@@ -185,6 +185,27 @@ QKD_API qkd_status qkd_qkd_ldpc_batch(const qkd_code *code, qkd_workspace *ws, c
                               uint8_t *bits_out, uint32_t *iterations, uint8_t *syndromes_match,
                               uint8_t *keys_match, void *stream);
 
+/* Bob's side of one-way LDPC reconciliation: sum_product_decoding_* exactly as
+ * QKD_LDPC_* calls it (qkd_ldpc_algorithm.cpp:398-431) with the target
+ * syndrome given by the caller instead of computed from Alice's key (Alice's
+ * half of the protocol is qkd_syndrome_batch on her key).
+ * bob[F*N] 0/1 bytes, syndrome[F*M] bytes (nonzero = 1, as qkd_decode_batch),
+ * one QBER for the batch. bits_out[F*N] (required): the last hard decision.
+ * corrected[F] (may be NULL): popcount(bits_out ^ bob) per frame. For every
+ * frame bits_out, iterations and syndromes_match equal what
+ * sum_product_decoding_irregular returns for llr_i = bob_i ? -log_p : +log_p,
+ * log_p = log((1-q)/q), and that syndrome; with syndrome = H * alice they
+ * equal qkd_qkd_ldpc_batch's on (alice, bob). Validation and flags as
+ * qkd_qkd_ldpc_batch. Runs that entry's decoders (folded first iteration,
+ * tables, speculation) except the frame-interleaved long-code decoder, which
+ * produces no decisions: codes of 65,536 < N <= 131,072 bits run the classic
+ * kernel here. */
+QKD_API qkd_status qkd_reconcile_batch(const qkd_code *code, qkd_workspace *ws, const uint8_t *bob,
+                               const uint8_t *syndrome, size_t n_frames, double qber,
+                               uint32_t max_iterations, double msg_threshold, uint32_t flags,
+                               uint8_t *bits_out, uint32_t *iterations, uint8_t *syndromes_match,
+                               uint32_t *corrected, void *stream);
+
 /* generate_random_bit_array + introduce_errors (array_and_matrix_operations.cpp:424-460)
  * for frame k seeded with seeds[k] + seed_offset (simulation.cpp:163,247),
  * on the device. alice/bob [F*N] 0/1 bytes; exact_qber[F] may be NULL.

@@ -11,6 +11,7 @@ src/array_and_matrix_operations.hpp) with batched, device-resident arrays:
   calculate_syndrome_irregular/_regular           calculate_syndrome(H, bits)
   sum_product_decoding_irregular/_regular         sum_product_decoding(H, llr, syndrome, ...)
   QKD_LDPC_irregular/_regular                     qkd_ldpc(H, alice, bob, qber, ...)
+  its decode step alone, Bob's side of a link      reconcile(H, bob, syndrome, qber, ...)
   generate_random_bit_array + introduce_errors    keygen(H, seeds, q_nominal, ...)
   run_trial over a batch + the batch reduction    run_trials(H, seeds, q_nominal, ...)
   seeds of QKD_LDPC_batch_simulation              make_seeds(simulation_seed, count)
@@ -40,7 +41,7 @@ __all__ = [
     "sum_product_decoding_irregular", "sum_product_decoding_regular", "qkd_ldpc",
     "QKD_LDPC_irregular", "QKD_LDPC_regular", "keygen", "run_trials", "make_seeds",
     "qber_range", "Workspace", "counters_to_stats", "decoder_flags", "trace_decode", "set_debug_option",
-    "spec_replays", "check_lanes", "interactive_simulation",
+    "spec_replays", "check_lanes", "interactive_simulation", "reconcile", "ReconcileResult",
 ]
 
 
@@ -334,6 +335,43 @@ def qkd_ldpc(H: HMatrix, alice, bob, qber: float, max_iterations: int = 50,
 
 QKD_LDPC_irregular = qkd_ldpc
 QKD_LDPC_regular = qkd_ldpc
+
+
+@dataclass
+class ReconcileResult:
+    """Bob's view of one reconciliation, one entry per frame: SP_result
+    (qkd_ldpc_algorithm.hpp:14-18) with the decoded key and the number of bits
+    the decoder changed in Bob's key (None when not asked for)."""
+    iterations: "torch.Tensor"
+    syndromes_match: "torch.Tensor"
+    bits: "torch.Tensor"
+    corrected: "torch.Tensor | None"
+
+
+def reconcile(H: HMatrix, bob, syndrome, qber: float, max_iterations: int = 50,
+              msg_threshold: float = 100.0, threshold_enabled: bool = True,
+              want_corrected: bool = True, workspace=None, stream=None,
+              variant: str = "sp_f64", minsum_scale: float | None = None,
+              minsum_offset: float | None = None, minsum_self_correct: bool = False) -> ReconcileResult:
+    """Bob's side of one-way reconciliation (qkd_reconcile_batch): the decode step of
+    QKD_LDPC_irregular/_regular (qkd_ldpc_algorithm.cpp:398-431) with the target syndrome
+    received from Alice (her half is calculate_syndrome on her key) instead of computed
+    from her key. bob [F, N] uint8 (0/1), syndrome [F, M] uint8 (nonzero = 1); one QBER
+    for the batch. bits: the last hard decision; corrected: popcount(bits ^ bob)."""
+    _need_cuda(bob, torch.uint8, "bob", H)
+    _need_cuda(syndrome, torch.uint8, "syndrome", H)
+    f = _frames(bob, H.num_bit_nodes, "bob")
+    _frames(syndrome, H.num_check_nodes, "syndrome", f)
+    dev = bob.device
+    bits = torch.empty((f, H.num_bit_nodes), dtype=torch.uint8, device=dev)
+    iters = torch.empty(f, dtype=torch.int32, device=dev)
+    ok = torch.empty(f, dtype=torch.uint8, device=dev)
+    corrected = torch.empty(f, dtype=torch.int32, device=dev) if want_corrected else None
+    flags = decoder_flags(threshold_enabled, variant, minsum_scale, minsum_offset, minsum_self_correct)
+    N.check(N.lib().qkd_reconcile_batch(H.handle, _ws(workspace), _ptr(bob), _ptr(syndrome), f, qber,
+                                        max_iterations, msg_threshold, flags, _ptr(bits), _ptr(iters),
+                                        _ptr(ok), _ptr(corrected), _stream(stream, H.device)))
+    return ReconcileResult(iters, ok, bits, corrected)
 
 
 def keygen(H: HMatrix, seeds, q_nominal: float, seed_offset: int = 0, workspace=None,

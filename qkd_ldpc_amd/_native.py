@@ -65,6 +65,7 @@ EXPORTS = [
     "qkd_interactive_batch",
     "qkd_code_from_alist_ex", "qkd_debug_decoder_timing", "qkd_debug_bit_order",
     "qkd_counters_merge", "qkd_debug_set_option", "qkd_debug_check_lanes",
+    "qkd_reconcile_batch",
 ]
 
 
@@ -121,6 +122,7 @@ def lib():
             "qkd_syndrome_batch": (st, [P, P, SZ, P, P]),
             "qkd_decode_batch": (st, [P, P, P, P, SZ, U32, D, U32, P, P, P, P]),
             "qkd_qkd_ldpc_batch": (st, [P, P, P, P, SZ, D, U32, D, U32, P, P, P, P, P]),
+            "qkd_reconcile_batch": (st, [P, P, P, P, SZ, D, U32, D, U32, P, P, P, P, P]),
             "qkd_keygen_batch": (st, [P, P, P, U64, SZ, D, P, P, P, P]),
             "qkd_trials_batch": (st, [P, P, P, U64, SZ, D, U32, D, U32, P, P, P, P, P, P]),
             "qkd_counters_batch": (st, [P, P, P, SZ, P, C.c_int, P]),

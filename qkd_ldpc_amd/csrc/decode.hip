@@ -32,6 +32,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "qkd_args.h"
 #include "qkd_internal.h"
 #include "qkd_math.h"
 #include "qkd_plan.h"
@@ -348,10 +349,13 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
         // ---- prologue: the frame's Alice and Bob words staged in LDS (the tanh
         //      rows are free until the first check phase)
         const uint64_t* sw = reinterpret_cast<const uint64_t*>(smem + L.tval);   // [alice | bob]
+        // (the target syndrome given by the caller, qkd_reconcile_batch:
+        // Bob's words only; uniform over the launch)
+        const bool given = MODE == kModeKeys && a.syn != nullptr;
         if (MODE == kModeKeys) {
             uint64_t* w = reinterpret_cast<uint64_t*>(smem + L.tval);
             for (int q = tid; q < (int)a.words; q += kDecodeBlock) {
-                w[q] = a.alice_w[(size_t)f * a.words + q];
+                if (!given) w[q] = a.alice_w[(size_t)f * a.words + q];
                 w[a.words + q] = a.bob_w[(size_t)f * a.words + q];
             }
             __syncthreads();
@@ -401,7 +405,7 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
                 for (int k = 0; k < DC; ++k) {
                     const int bit = bl[k];
                     if (bit >= 0) {
-                        pa ^= (uint32_t)(sw[bit >> 6] >> (bit & 63));
+                        if (!given) pa ^= (uint32_t)(sw[bit >> 6] >> (bit & 63));
                         pb ^= (uint32_t)(sw[a.words + (bit >> 6)] >> (bit & 63));
                         deg++;
                     }
@@ -410,12 +414,14 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
                     for (int k = DC; k < c.max_dc; ++k) {
                         const int bit = c.chk_bits[k * c.m_pad + j];
                         if (bit >= 0) {
-                            pa ^= (uint32_t)(sw[bit >> 6] >> (bit & 63));
+                            if (!given) pa ^= (uint32_t)(sw[bit >> 6] >> (bit & 63));
                             pb ^= (uint32_t)(sw[a.words + (bit >> 6)] >> (bit & 63));
                             deg++;
                         }
                     }
                 }
+                // (given: s_j is the caller's byte, Alice's parity is not computed)
+                if (given) pa = (ok && a.syn[(size_t)f * c.m + j] != 0) ? 1u : 0u;
                 sj = (int)(pa & 1u);
                 qj = (int)((pa ^ pb ^ (lsign & deg)) & 1u);
             }
@@ -586,7 +592,7 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
         for (int i = tid; i < c.n; i += kDecodeBlock) {
             const uint8_t d = total[i] <= 0 ? 1 : 0;
             if (a.bits_out) a.bits_out[(size_t)f * c.n + i] = d;
-            if (MODE == kModeKeys) {
+            if (MODE == kModeKeys && !given) {
                 const uint64_t w = a.alice_w[(size_t)f * a.words + (i >> 6)];
                 key_mismatch |= (uint8_t)((w >> (i & 63)) & 1u) != d;
             }
@@ -669,6 +675,13 @@ hipError_t launch_pack_keys(const DecodeArgs& a, hipStream_t stream) {
     const bool wide = (n % 32) == 0 &&
                       ((reinterpret_cast<uintptr_t>(a.alice_b) | reinterpret_cast<uintptr_t>(a.bob_b)) & 15u) == 0;
     const size_t threads = wide ? nw * 2 : nw * 8;
+    if (!a.alice_b) {
+        // Bob's key alone (qkd_reconcile_batch): one grid row, alice_w untouched
+        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((threads + 255) / 256), 1), dim3(256), 0, stream,
+                           a.bob_b, a.bob_b, n, a.words, a.n_frames, const_cast<uint64_t*>(a.bob_w),
+                           const_cast<uint64_t*>(a.bob_w), wide ? 1u : 0u);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((threads + 255) / 256), 2), dim3(256), 0, stream,
                        a.alice_b, a.bob_b, n, a.words, a.n_frames, const_cast<uint64_t*>(a.alice_w),
                        const_cast<uint64_t*>(a.bob_w), wide ? 1u : 0u);
@@ -1637,8 +1650,10 @@ static qkd_status check_no_static_lds(DecodeFn fn) {
     return QKD_OK;
 }
 
+// corrected (qkd_reconcile_batch, or nullptr): popcount(bits_out ^ bob) per
+// frame, from the kernel that follows the decoder
 static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs& a, int mode,
-                                uint32_t flags, hipStream_t stream) {
+                                uint32_t flags, hipStream_t stream, uint32_t* corrected = nullptr) {
     int dc = 0;
     int rule = rule_of(flags);
     // QKD_MINSUM_STORE=global keeps the global-message-store min-sum (tests)
@@ -1960,7 +1975,7 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
                 hipLaunchKernelGGL(sfn, dim3(grid), dim3(kDecodeBlock), L.bytes, stream, a);
                 QKD_HIP(decoder_event_close(ws, stream, hipGetLastError()));
             }
-            if (mode == kModeKeys) QKD_HIP(launch_key_match(a, stream));
+            if (mode == kModeKeys) QKD_HIP(launch_key_match(a, stream, corrected));
             return QKD_OK;
         }
     }
@@ -1982,7 +1997,7 @@ classic_path:
     if (s != QKD_OK) return s;
     a.code = c->view();
     // (byte keys: the classic kernel reads them packed, in the original order)
-    if (mode == kModeKeys && a.alice_b) QKD_HIP(launch_pack_keys(a, stream));
+    if (mode == kModeKeys && a.bob_b) QKD_HIP(launch_pack_keys(a, stream));
     a.c2b = ws->c2b;
     a.c2b_stride = (size_t)c->max_dv * c->n_pad;
     // the workspace holds one total row per slot after all the message stores
@@ -1999,6 +2014,8 @@ classic_path:
     QKD_HIP(decoder_event(ws, stream));
     hipLaunchKernelGGL(fn, dim3(grid), dim3(kDecodeBlock), lds, stream, a);
     QKD_HIP(decoder_event_close(ws, stream, hipGetLastError()));
+    // (the classic kernel wrote bits_out itself)
+    if (corrected) QKD_HIP(launch_count_flips(a.bits_out, a.bob_b, (uint32_t)c->n, a.n_frames, corrected, stream));
     return QKD_OK;
 }
 
@@ -2119,14 +2136,19 @@ static SpecClean& spec_clean_of(qkd_workspace* ws, double q) {
     return ws->spec_clean[q];
 }
 
-// Shared by qkd_qkd_ldpc_batch and qkd_trials_batch: keys already packed in ws.
+// Shared by qkd_qkd_ldpc_batch, qkd_trials_batch and qkd_reconcile_batch: keys
+// already packed in ws, or byte keys. syn (qkd_reconcile_batch): the target
+// syndrome given by the caller, with bob_b alone (alice_b and key_ok nullptr);
+// corrected: its flip counts.
 static qkd_status decode_keys(const qkd_code* c, qkd_workspace* ws, size_t n_frames, double q,
                               uint32_t max_it, double thr, uint32_t flags, uint8_t* bits_out,
                               uint32_t* iters, uint8_t* sp_ok, uint8_t* key_ok, hipStream_t stream,
-                              const uint8_t* alice_b = nullptr, const uint8_t* bob_b = nullptr) {
+                              const uint8_t* alice_b = nullptr, const uint8_t* bob_b = nullptr,
+                              const uint8_t* syn = nullptr, uint32_t* corrected = nullptr) {
     DecodeArgs a{};
     a.alice_b = alice_b;
     a.bob_b = bob_b;
+    a.syn = syn;
     a.pinf = std::numeric_limits<float>::infinity();
     a.n_frames = (uint32_t)n_frames;
     a.max_it = max_it;
@@ -2194,7 +2216,7 @@ static qkd_status decode_keys(const qkd_code* c, qkd_workspace* ws, size_t n_fra
         a.ckpt_unsat = (uint32_t)cu;
         if (cu == 0) a.spec_cap = 0;
     }
-    qkd_status st = launch_decode(c, ws, a, kModeKeys, flags, stream);
+    qkd_status st = launch_decode(c, ws, a, kModeKeys, flags, stream, corrected);
     if (st != QKD_OK || a.spec_cap == 0 || a.ckpt_unsat || ws->spec_stat_pending) return st;
     // (a QBER whose last two samples stayed under the switch is sampled again
     // only every kSpecStatEvery calls: each sample is a device-to-host copy
@@ -2239,6 +2261,29 @@ qkd_status qkd_qkd_ldpc_batch(const qkd_code* c, qkd_workspace* ws, const uint8_
     // path inside its frame-syndrome kernel, launch_frame_syn)
     return decode_keys(c, ws, n_frames, qber, max_iterations, msg_threshold, flags, bits_out, iterations,
                        syndromes_match, keys_match, (hipStream_t)stream, alice, bob);
+}
+
+qkd_status qkd_reconcile_batch(const qkd_code* c, qkd_workspace* ws, const uint8_t* bob,
+                               const uint8_t* syndrome, size_t n_frames, double qber, uint32_t max_iterations,
+                               double msg_threshold, uint32_t flags, uint8_t* bits_out, uint32_t* iterations,
+                               uint8_t* syndromes_match, uint32_t* corrected, void* stream) {
+    clear_error();
+    if (const char* bad = qkda::reconcile_args_error(c, bob, syndrome, n_frames, qber, bits_out, iterations,
+                                                     syndromes_match))
+        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    qkd_status s = check_decode_params(max_iterations, msg_threshold, flags);
+    if (s != QKD_OK) return s;
+    DeviceGuard g(c->device);
+    ws = resolve_ws(c, ws);
+    if (!ws) return set_error(QKD_ERR_OUT_OF_MEMORY, "no workspace");
+    WsSession sess(ws, (hipStream_t)stream);
+    s = ws_reserve_keys(ws, n_frames, 1);
+    if (s != QKD_OK) return s;
+    // keys mode with the target given: no Alice key, no key compare (the
+    // interleaved long-code decoder, which has no decisions to give, is
+    // excluded by bits_out; codes it alone takes run the classic kernel)
+    return decode_keys(c, ws, n_frames, qber, max_iterations, msg_threshold, flags, bits_out, iterations,
+                       syndromes_match, nullptr, (hipStream_t)stream, nullptr, bob, syndrome, corrected);
 }
 
 static qkd_status keygen_into_ws(const qkd_code* c, qkd_workspace* ws, const uint64_t* seeds,

@@ -2192,6 +2192,79 @@ __global__ __launch_bounds__(kSynBlock) void frame_syn_kernel(DeviceCode c, uint
     }
 }
 
+// frame_syn_kernel with the target syndrome given by the caller
+// (qkd_reconcile_batch: syn_b[F x M] bytes, nonzero = 1; rows of any
+// alignment): only Bob's words are staged ([kSynFrames][2 * words] 32-bit
+// words), only (H * bob)_j is computed, and only bob_w is rewritten in the
+// internal order. The queue and window resets, q_j and the layout of synw are
+// frame_syn_kernel's.
+__global__ __launch_bounds__(kSynBlock) void frame_syn_given_kernel(DeviceCode c, uint64_t* bob_w,
+                                                                    const uint8_t* syn_b, uint32_t words,
+                                                                    uint32_t n_frames, uint32_t lsign,
+                                                                    uint32_t* synw, uint32_t* counter,
+                                                                    uint32_t* win, uint32_t win_words) {
+    extern __shared__ uint32_t kb[];
+    if (blockIdx.x == 0 && threadIdx.x < 2) counter[threadIdx.x] = 0;
+    for (uint32_t i = blockIdx.x * kSynBlock + threadIdx.x; i < win_words; i += gridDim.x * kSynBlock) win[i] = 0;
+    const uint32_t w32 = 2 * words;
+    const uint32_t f0 = blockIdx.x * kSynFrames;
+    const uint32_t nf = min((uint32_t)kSynFrames, n_frames - f0);
+    for (uint32_t q = threadIdx.x; q < (uint32_t)kSynFrames * words; q += kSynBlock) {
+        const uint32_t fr = q / words;
+        const uint32_t w = q - fr * words;
+        const uint64_t bv = fr < nf ? bob_w[(size_t)(f0 + fr) * words + w] : 0ull;
+        kb[fr * w32 + 2 * w] = (uint32_t)bv;
+        kb[fr * w32 + 2 * w + 1] = (uint32_t)(bv >> 32);
+    }
+    __syncthreads();
+    const int m_words = decode_m_words(c.m);
+    const int lane = threadIdx.x & 63;
+    for (int j0 = (int)(threadIdx.x & ~63u); j0 < c.m; j0 += kSynBlock) {
+        const int j = j0 + lane;
+        uint32_t pb[kSynFrames], sj[kSynFrames];
+#pragma unroll
+        for (int fr = 0; fr < kSynFrames; ++fr) pb[fr] = sj[fr] = 0;
+        uint32_t deg = 0;
+        if (j < c.m) {
+#pragma unroll
+            for (int fr = 0; fr < kSynFrames; ++fr)
+                sj[fr] = ((uint32_t)fr < nf && syn_b[(size_t)(f0 + fr) * (uint32_t)c.m + j] != 0) ? 1u : 0u;
+            for (int k = 0; k < c.max_dc; ++k) {
+                const int bit = c.chk_bits[k * c.m_pad + j];
+                if (bit < 0) continue;
+                deg++;
+                const uint32_t wi = (uint32_t)bit >> 5, sh = (uint32_t)bit & 31u;
+#pragma unroll
+                for (int fr = 0; fr < kSynFrames; ++fr) pb[fr] ^= kb[fr * w32 + wi] >> sh;
+            }
+        }
+#pragma unroll
+        for (int fr = 0; fr < kSynFrames; ++fr) {
+            const uint64_t sm = __ballot(sj[fr]);
+            const uint64_t qm = __ballot((sj[fr] ^ pb[fr] ^ (lsign & deg)) & 1u);
+            if (lane == 0 && (uint32_t)fr < nf) {
+                uint32_t* o = synw + (size_t)(f0 + fr) * 2 * m_words;
+                o[j0 >> 5] = (uint32_t)sm;
+                o[(j0 >> 5) + 1] = (uint32_t)(sm >> 32);
+                o[m_words + (j0 >> 5)] = (uint32_t)qm;
+                o[m_words + (j0 >> 5) + 1] = (uint32_t)(qm >> 32);
+            }
+        }
+    }
+    // Bob's key in the internal order: word w's lane l takes original bit
+    // perm[64 w + l]; one ballot per frame
+    for (uint32_t w = threadIdx.x >> 6; w < words; w += kSynBlock / 64) {
+        const uint32_t q = w * 64 + (uint32_t)lane;
+        const bool in = q < (uint32_t)c.n;
+        const uint32_t o = in ? (uint32_t)c.perm[q] : 0u;
+#pragma unroll
+        for (int fr = 0; fr < kSynFrames; ++fr) {
+            const uint64_t bm = __ballot(in && ((kb[fr * w32 + (o >> 5)] >> (o & 31u)) & 1u));
+            if (lane == 0 && (uint32_t)fr < nf) bob_w[(size_t)(f0 + fr) * words + w] = bm;
+        }
+    }
+}
+
 // bits_out[f][bit] from the decoder's packed decisions in the internal bit
 // order (DeviceCode::inv)
 __global__ void zout_unpack_kernel(const uint64_t* zout, const int32_t* inv, uint32_t n, uint32_t words,
@@ -2201,6 +2274,67 @@ __global__ void zout_unpack_kernel(const uint64_t* zout, const int32_t* inv, uin
     const size_t f = gid / n;
     const uint32_t q = (uint32_t)inv[gid - f * n];
     out[gid] = (uint8_t)((zout[f * words + (q >> 6)] >> (q & 63)) & 1u);
+}
+
+// The sum of v over the workgroup's threads, at thread 0 (red: one word per wave).
+constexpr int kCountBlock = 256;
+__device__ __forceinline__ uint32_t count_block_sum(uint32_t v, uint32_t* red) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s);
+    if ((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint32_t t = 0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < kCountBlock / 64; ++w) t += red[w];
+    return t;
+}
+
+// zout_unpack_kernel for qkd_reconcile_batch with a corrected[] output: a
+// workgroup per frame stages the frame's decision words in LDS, writes
+// bits_out through inv and counts the positions where the decision differs
+// from Bob's byte key (original order): corrected[f] = popcount(bits_out ^
+// bob), no atomics. quad (the host's choice: N % 4 == 0, bob and out 4-byte
+// aligned): four positions per thread and pass, one 4-byte load and store.
+__global__ __launch_bounds__(kCountBlock) void zout_unpack_count_kernel(const uint64_t* zout, const int32_t* inv,
+                                                                        uint32_t n, uint32_t words,
+                                                                        const uint8_t* bob, uint8_t* out,
+                                                                        uint32_t* corrected, uint32_t quad) {
+    extern __shared__ uint64_t zf[];
+    __shared__ uint32_t red[kCountBlock / 64];
+    const size_t f = blockIdx.x;
+    for (uint32_t w = threadIdx.x; w < words; w += kCountBlock) zf[w] = zout[f * words + w];
+    __syncthreads();
+    auto bit_at = [&](int32_t q) -> uint32_t { return (uint32_t)(zf[(uint32_t)q >> 6] >> ((uint32_t)q & 63u)) & 1u; };
+    uint32_t cnt = 0;
+    if (quad) {
+        for (uint32_t i = threadIdx.x * 4; i < n; i += kCountBlock * 4) {
+            const int4 q = *reinterpret_cast<const int4*>(inv + i);
+            const uint32_t d = bit_at(q.x) | (bit_at(q.y) << 8) | (bit_at(q.z) << 16) | (bit_at(q.w) << 24);
+            const uint32_t b = *reinterpret_cast<const uint32_t*>(bob + f * n + i) & 0x01010101u;
+            *reinterpret_cast<uint32_t*>(out + f * n + i) = d;
+            cnt += (uint32_t)__popc(d ^ b);
+        }
+    } else {
+        for (uint32_t i = threadIdx.x; i < n; i += kCountBlock) {
+            const uint32_t d = bit_at(inv[i]);
+            out[f * n + i] = (uint8_t)d;
+            cnt += d ^ (uint32_t)(bob[f * n + i] & 1u);
+        }
+    }
+    const uint32_t total = count_block_sum(cnt, red);
+    if (threadIdx.x == 0) corrected[f] = total;
+}
+
+// The classic kernel writes bits_out itself: corrected[f] = popcount(bits_out
+// ^ bob) of a frame per workgroup (qkd_reconcile_batch, corrected != NULL).
+__global__ __launch_bounds__(kCountBlock) void count_flips_kernel(const uint8_t* bits, const uint8_t* bob, uint32_t n,
+                                                                  uint32_t* corrected) {
+    __shared__ uint32_t red[kCountBlock / 64];
+    const size_t f = blockIdx.x;
+    uint32_t cnt = 0;
+    for (uint32_t i = threadIdx.x; i < n; i += kCountBlock) cnt += (uint32_t)((bits[f * n + i] ^ bob[f * n + i]) & 1u);
+    const uint32_t total = count_block_sum(cnt, red);
+    if (threadIdx.x == 0) corrected[f] = total;
 }
 
 // frame_syn_kernel's work bit-sliced over frames: a workgroup takes 16
@@ -2243,14 +2377,21 @@ __device__ __forceinline__ uint32_t wave_transpose32(uint32_t x, uint32_t lane) 
 // (v & 0x01010101) << f gathers 8 frames' bits of 4 positions into the 4
 // bytes of one word, and v_perm_b32 assembles each position's slice from the
 // four words (Alice frames 0-7 / 8-15, Bob frames 0-7 / 8-15).
-template <bool BYTES>
+// GIVEN (qkd_reconcile_batch): the target syndrome comes from the caller's
+// bytes syn_b[F x M] (nonzero = 1) instead of from Alice's key. Only Bob's key
+// is loaded, sliced and rewritten (the Alice halves of the slices stay 0;
+// alice_w / alice_b are neither read nor written), and in step 2 the lane of
+// check j reads its 16 frames' bytes (consecutive lanes, consecutive bytes; no
+// alignment of the rows assumed) in place of the low half of P.
+template <bool BYTES, bool GIVEN = false>
 __global__ __launch_bounds__(kSlicedBlock) void frame_syn_sliced_kernel(DeviceCode c, uint64_t* alice_w,
                                                                         uint64_t* bob_w, uint32_t words,
                                                                         uint32_t n_frames, uint32_t lsign,
                                                                         uint32_t* synw, uint32_t* counter,
                                                                         uint32_t* win, uint32_t win_words,
                                                                         const uint8_t* alice_b,
-                                                                        const uint8_t* bob_b) {
+                                                                        const uint8_t* bob_b,
+                                                                        const uint8_t* syn_b) {
     extern __shared__ uint32_t T[];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // (uniform to the compiler)
@@ -2269,6 +2410,8 @@ __global__ __launch_bounds__(kSlicedBlock) void frame_syn_sliced_kernel(DeviceCo
     auto load_pair = [&](uint32_t p) -> uint64_t {
         const uint32_t w = 2 * p + half;
         if (p >= pairs || w >= words || fr >= nf) return 0;
+        if constexpr (GIVEN)
+            if (!bob_lane) return 0;
         return (bob_lane ? bob_w : alice_w)[(size_t)(f0 + fr) * words + w];
     };
     auto slice_pair = [&](uint32_t p, uint64_t v) {
@@ -2290,7 +2433,8 @@ __global__ __launch_bounds__(kSlicedBlock) void frame_syn_sliced_kernel(DeviceCo
 #pragma unroll
             for (uint32_t f = 0; f < (uint32_t)kSlicedFrames; ++f) {
                 const size_t off = (size_t)(f0 + f) * n + 8 * p;
-                va[f] = f < nf ? *reinterpret_cast<const uint2*>(alice_b + off) : make_uint2(0, 0);
+                if constexpr (GIVEN) va[f] = make_uint2(0, 0);
+                else va[f] = f < nf ? *reinterpret_cast<const uint2*>(alice_b + off) : make_uint2(0, 0);
                 vb[f] = f < nf ? *reinterpret_cast<const uint2*>(bob_b + off) : make_uint2(0, 0);
             }
             // x[key][frame half][position half]: byte k bit f' = that key's bit
@@ -2348,6 +2492,17 @@ __global__ __launch_bounds__(kSlicedBlock) void frame_syn_sliced_kernel(DeviceCo
                         deg++;
                     }
             }
+            if constexpr (GIVEN) {
+                // the caller's target bits of this check, frame f in bit f
+                uint8_t sb[kSlicedFrames];
+#pragma unroll
+                for (uint32_t f = 0; f < (uint32_t)kSlicedFrames; ++f)
+                    sb[f] = f < nf ? syn_b[(size_t)(f0 + f) * (uint32_t)c.m + j] : (uint8_t)0;
+                uint32_t tb = 0;
+#pragma unroll
+                for (uint32_t f = 0; f < (uint32_t)kSlicedFrames; ++f) tb |= (sb[f] != 0 ? 1u : 0u) << f;
+                P = (P & 0xffff0000u) | tb;
+            }
         }
         const uint32_t Q = P ^ (P >> 16) ^ ((lsign & deg) ? 0xffffu : 0u);   // low 16: q bits
         // transposed, lane f < 16 holds frame f's target bits of the 64 checks
@@ -2379,7 +2534,7 @@ __global__ __launch_bounds__(kSlicedBlock) void frame_syn_sliced_kernel(DeviceCo
         const uint32_t tr = wave_transpose32(S, lane);
         const uint32_t up = (uint32_t)__shfl_xor((int)tr, 32);
         const uint32_t g = lane & 15u;
-        if (lane < 32 && g < nf)
+        if (lane < 32 && g < nf && !(GIVEN && lane < 16))
             (lane < 16 ? alice_w : bob_w)[(size_t)(f0 + g) * words + w] = ((uint64_t)up << 32) | tr;
         pq = pn;
     }
@@ -2391,50 +2546,88 @@ hipError_t launch_frame_syn(const DecodeArgs& a, hipStream_t stream, bool gather
     // (gather, the QKD_SYN_SLICED option 0: frame_syn_kernel; tests compare the two)
     const size_t slds = (size_t)a.words * 64 * sizeof(uint32_t);
     const bool sliced = a.code.chk_rows16 && slds <= 160 * 1024 && !gather;
-    // byte keys (qkd_qkd_ldpc_batch): packed by the sliced kernel itself when
-    // their rows allow 8-byte loads (pack_first, the QKD_SYN_BYTES option 0: pack_kernel first;
-    // tests compare the two), else by pack_kernel
-    const bool bytes = a.alice_b && sliced && a.code.n % 8 == 0 &&
+    // the target syndrome given by the caller (qkd_reconcile_batch: a.syn set,
+    // no Alice key): the GIVEN kernels, Bob's key alone
+    const bool given = a.syn != nullptr;
+    // byte keys (qkd_qkd_ldpc_batch, qkd_reconcile_batch): packed by the sliced
+    // kernel itself when their rows allow 8-byte loads (pack_first, the
+    // QKD_SYN_BYTES option 0: pack_kernel first; tests compare the two), else
+    // by pack_kernel
+    const bool bytes = a.bob_b && sliced && a.code.n % 8 == 0 &&
                        ((reinterpret_cast<uintptr_t>(a.alice_b) | reinterpret_cast<uintptr_t>(a.bob_b)) & 7u) == 0 &&
                        !pack_first;
-    if (a.alice_b && !bytes) {
+    if (a.bob_b && !bytes) {
         const hipError_t e = launch_pack_keys(a, stream);
         if (e != hipSuccess) return e;
     }
     if (sliced) {
-        const void* fn = bytes ? (const void*)frame_syn_sliced_kernel<true> : (const void*)frame_syn_sliced_kernel<false>;
+        const void* fn = given ? (bytes ? (const void*)frame_syn_sliced_kernel<true, true>
+                                        : (const void*)frame_syn_sliced_kernel<false, true>)
+                               : (bytes ? (const void*)frame_syn_sliced_kernel<true>
+                                        : (const void*)frame_syn_sliced_kernel<false>);
         // (the attribute on every launch, for the current device, as decode_grid
         // does for the decoder: no process-wide flag to race on or to skip for
         // a second device)
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
         const dim3 grid((a.n_frames + kSlicedFrames - 1) / kSlicedFrames);
-        if (bytes)
+        if (given && bytes)
+            hipLaunchKernelGGL((frame_syn_sliced_kernel<true, true>), grid, dim3(kSlicedBlock), slds, stream, a.code,
+                               nullptr, const_cast<uint64_t*>(a.bob_w), a.words, a.n_frames, lsign,
+                               const_cast<uint32_t*>(a.synw), a.counter, a.win, 2 * a.win_count, nullptr, a.bob_b,
+                               a.syn);
+        else if (given)
+            hipLaunchKernelGGL((frame_syn_sliced_kernel<false, true>), grid, dim3(kSlicedBlock), slds, stream, a.code,
+                               nullptr, const_cast<uint64_t*>(a.bob_w), a.words, a.n_frames, lsign,
+                               const_cast<uint32_t*>(a.synw), a.counter, a.win, 2 * a.win_count, nullptr, nullptr,
+                               a.syn);
+        else if (bytes)
             hipLaunchKernelGGL(frame_syn_sliced_kernel<true>, grid, dim3(kSlicedBlock), slds, stream, a.code,
                                const_cast<uint64_t*>(a.alice_w), const_cast<uint64_t*>(a.bob_w), a.words,
                                a.n_frames, lsign, const_cast<uint32_t*>(a.synw), a.counter, a.win,
-                               2 * a.win_count, a.alice_b, a.bob_b);
+                               2 * a.win_count, a.alice_b, a.bob_b, nullptr);
         else
             hipLaunchKernelGGL(frame_syn_sliced_kernel<false>, grid, dim3(kSlicedBlock), slds, stream, a.code,
                                const_cast<uint64_t*>(a.alice_w), const_cast<uint64_t*>(a.bob_w), a.words,
                                a.n_frames, lsign, const_cast<uint32_t*>(a.synw), a.counter, a.win,
-                               2 * a.win_count, nullptr, nullptr);
+                               2 * a.win_count, nullptr, nullptr, nullptr);
+        return hipGetLastError();
+    }
+    const dim3 ggrid((a.n_frames + kSynFrames - 1) / kSynFrames);
+    if (given) {
+        const size_t glds = (size_t)kSynFrames * 2 * a.words * sizeof(uint32_t);
+        hipLaunchKernelGGL(frame_syn_given_kernel, ggrid, dim3(kSynBlock), glds, stream, a.code,
+                           const_cast<uint64_t*>(a.bob_w), a.syn, a.words, a.n_frames, lsign,
+                           const_cast<uint32_t*>(a.synw), a.counter, a.win, 2 * a.win_count);
         return hipGetLastError();
     }
     const size_t lds = (size_t)kSynFrames * 2 * a.words * sizeof(uint64_t);
-    hipLaunchKernelGGL(frame_syn_kernel, dim3((a.n_frames + kSynFrames - 1) / kSynFrames), dim3(kSynBlock), lds,
+    hipLaunchKernelGGL(frame_syn_kernel, ggrid, dim3(kSynBlock), lds,
                        stream, a.code, const_cast<uint64_t*>(a.alice_w), const_cast<uint64_t*>(a.bob_w), a.words,
                        a.n_frames, lsign, const_cast<uint32_t*>(a.synw), a.counter, a.win, 2 * a.win_count);
     return hipGetLastError();
 }
 
-hipError_t launch_key_match(const DecodeArgs& a, hipStream_t stream) {
+hipError_t launch_key_match(const DecodeArgs& a, hipStream_t stream, uint32_t* corrected) {
     // (decode_split_kernel compares the keys itself: keys_match needs no launch)
-    if (a.bits_out) {
+    if (a.bits_out && corrected) {
+        // qkd_reconcile_batch: the unpack that also counts the flips against Bob's bytes
+        const uint32_t n = (uint32_t)a.code.n;
+        const bool quad = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(a.bob_b) |
+                                          reinterpret_cast<uintptr_t>(a.bits_out)) & 3u) == 0;
+        hipLaunchKernelGGL(zout_unpack_count_kernel, dim3(a.n_frames), dim3(kCountBlock), (size_t)a.words * 8, stream,
+                           a.zout, a.code.inv, n, a.words, a.bob_b, a.bits_out, corrected, quad ? 1u : 0u);
+    } else if (a.bits_out) {
         const size_t total = (size_t)a.n_frames * a.code.n;
         hipLaunchKernelGGL(zout_unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a.zout,
                            a.code.inv, (uint32_t)a.code.n, a.words, a.n_frames, a.bits_out);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_count_flips(const uint8_t* bits, const uint8_t* bob, uint32_t n, uint32_t n_frames,
+                              uint32_t* corrected, hipStream_t stream) {
+    hipLaunchKernelGGL(count_flips_kernel, dim3(n_frames), dim3(kCountBlock), 0, stream, bits, bob, n, corrected);
     return hipGetLastError();
 }
 

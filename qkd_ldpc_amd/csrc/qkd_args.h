@@ -1,0 +1,26 @@
+// qkd_args.h — host-only argument checks of the batched entry points, free of
+// HIP so that a stand-alone host program can exercise them
+// (tests/native/reconcile_args_check.cpp).
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+namespace qkda {
+
+// qkd_reconcile_batch's own arguments (the decode parameters and flags are
+// check_decode_params', as for qkd_qkd_ldpc_batch): nullptr when they are
+// acceptable, else the message of the QKD_ERR_INVALID_ARG to return.
+// corrected may be NULL and is not looked at. The QBER test is written so
+// that a NaN fails it.
+inline const char* reconcile_args_error(const void* code, const uint8_t* bob, const uint8_t* syndrome,
+                                        size_t n_frames, double qber, const uint8_t* bits_out,
+                                        const uint32_t* iterations, const uint8_t* syndromes_match) {
+    if (!code || !bob || !syndrome || !bits_out || !iterations || !syndromes_match) return "null argument";
+    if (n_frames == 0) return "n_frames must be > 0";
+    if (n_frames > 0xffffffffull) return "n_frames too large";
+    if (!(qber > 0.0 && qber < 1.0)) return "QBER must be in (0,1)";
+    return nullptr;
+}
+
+}  // namespace qkda

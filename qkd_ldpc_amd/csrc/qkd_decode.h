@@ -78,6 +78,10 @@ struct DecodeArgs {
     int ms_sc;         // kRuleMinSumLds: self-corrected (QKD_MINSUM_SELF_CORRECT)
     // kModeLlr
     const double* llr;
+    // the caller's target syndrome bytes (F x M, nonzero = 1): kModeLlr, and
+    // kModeKeys when the target is given instead of computed from Alice's key
+    // (qkd_reconcile_batch: alice_b and key_ok are nullptr, alice_w is neither
+    // read nor written); nullptr on the other keys-path calls
     const uint8_t* syn;
     // kModeKeys
     const uint64_t* alice_w;
@@ -688,9 +692,16 @@ DecodeFn pick_ilv(int rs, int max_dc, bool tsyn_global, bool xunc_global = false
 // Before: a.synw from the packed keys. After: key_ok / bits_out from a.zout.
 // gather: the gather kernel instead of the bit-sliced one; pack_first: byte
 // keys packed by pack_kernel first (the QKD_SYN_SLICED / QKD_SYN_BYTES options)
+// a.syn set (qkd_reconcile_batch): the given-target kernels, Bob's key alone.
 hipError_t launch_frame_syn(const DecodeArgs& a, hipStream_t stream, bool gather = false, bool pack_first = false);
-// decode.hip: a.alice_b / a.bob_b -> a.alice_w / a.bob_w (original bit order)
+// decode.hip: a.alice_b / a.bob_b -> a.alice_w / a.bob_w (original bit order);
+// a.alice_b == nullptr: Bob's key alone
 hipError_t launch_pack_keys(const DecodeArgs& a, hipStream_t stream);
-hipError_t launch_key_match(const DecodeArgs& a, hipStream_t stream);
+// corrected (qkd_reconcile_batch, with a.bits_out and a.bob_b): the unpack
+// also writes popcount(bits_out ^ bob) per frame
+hipError_t launch_key_match(const DecodeArgs& a, hipStream_t stream, uint32_t* corrected = nullptr);
+// the same count after the classic kernel, which writes bits_out itself
+hipError_t launch_count_flips(const uint8_t* bits, const uint8_t* bob, uint32_t n, uint32_t n_frames,
+                              uint32_t* corrected, hipStream_t stream);
 
 }  // namespace qkd
