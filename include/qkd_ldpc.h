@@ -206,6 +206,67 @@ QKD_API qkd_status qkd_reconcile_batch(const qkd_code *code, qkd_workspace *ws, 
                                uint8_t *bits_out, uint32_t *iterations, uint8_t *syndromes_match,
                                uint32_t *corrected, void *stream);
 
+/* ---- key verification ------------------------------------------------------
+ * After error correction Alice announces a short universal-hash tag of her
+ * key; Bob hashes his corrected key and compares; a frame whose tags differ is
+ * thrown away. (syndromes_match alone cannot tell: a decoder that converges to
+ * a different word with the same syndrome reports 1.)
+ *
+ * The hash is a Hankel (Toeplitz-family) matrix over GF(2), given by a key
+ * string R of W = qkd_verify_key_words(N) = ceil((N + 63) / 64) 64-bit words.
+ * Bit k of the string is r[k] = (R[k >> 6] >> (k & 63)) & 1, 0 <= k <= N + 62;
+ * the window W(p), 0 <= p < N, is the 64-bit word whose bit i is r[p + i];
+ *   tag(x) = XOR over the positions p with x_p = 1 of W(p), low tag_bits bits
+ * (tag bit i = XOR_p r[p + i] x_p). A t-bit tag is the low t bits of the 64-bit
+ * tag, 1 <= tag_bits <= 64; the all-zero key has tag 0. Positions are the
+ * caller's original bit positions; a key bit is byte & 1.
+ *
+ * R is the caller's hash_words[W] (device memory; truly random bits shared by
+ * Alice and Bob: the form for which the family is 2^-t universal), or, with
+ * hash_words == NULL, expanded from the 64-bit hash_seed by SplitMix64 in
+ * counter form:
+ *   R[k] = mix(hash_seed + (k + 1) * 0x9E3779B97F4A7C15)   (mod 2^64)
+ *   mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *           z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ * The seeded form is a computational stand-in, NOT an information-theoretic
+ * one: its key string has at most 64 bits of entropy. In either form a tag
+ * discloses tag_bits bits of the key, which the caller's privacy amplification
+ * has to account for. */
+
+/* W, the number of 64-bit words of the key string for an N-bit key (0 for
+ * n_bits < 1). Host only. */
+QKD_API size_t qkd_verify_key_words(int32_t n_bits);
+
+/* The W words the seeded form uses, into host memory (to inspect them, or to
+ * upload them as hash_words). Host only, no device work. */
+QKD_API qkd_status qkd_verify_expand_key(uint64_t hash_seed, int32_t n_bits, uint64_t *words_host);
+
+/* Alice's half (and anyone's who holds byte keys): tags[f] = tag(bits[f]) for
+ * bits[F*N] 0/1 bytes on the device (only byte & 1 counts; rows of any
+ * alignment). One kernel launch on the stream, no workspace, no host copy, no
+ * synchronisation: capturable in a graph. */
+QKD_API qkd_status qkd_verify_tags_batch(const qkd_code *code, const uint8_t *bits, size_t n_frames,
+                               uint64_t hash_seed, const uint64_t *hash_words, uint32_t tag_bits,
+                               uint64_t *tags, void *stream);
+
+/* Bob's half: qkd_reconcile_batch (same arguments, same order, and bit for bit
+ * the same bits_out, iterations, syndromes_match and corrected) followed by
+ * verification of the corrected key, in the kernel that writes bits_out where
+ * the decoder has one. tags_out[F] (may be NULL): tag(bits_out[f]), masked.
+ * alice_tags[F] (may be NULL): Alice's announced tags; then verified[F]
+ * (required exactly when alice_tags is given):
+ *   verified[f] = syndromes_match[f] && ((tag ^ alice_tags[f]) & mask) == 0.
+ * QKD_ERR_INVALID_ARG, before any device work, when both alice_tags and
+ * tags_out are NULL, when tag_bits is outside 1..64, or when verified and
+ * alice_tags are not given together. */
+QKD_API qkd_status qkd_reconcile_verify_batch(const qkd_code *code, qkd_workspace *ws, const uint8_t *bob,
+                               const uint8_t *syndrome, size_t n_frames, double qber,
+                               uint32_t max_iterations, double msg_threshold, uint32_t flags,
+                               uint8_t *bits_out, uint32_t *iterations, uint8_t *syndromes_match,
+                               uint32_t *corrected, uint64_t hash_seed, const uint64_t *hash_words,
+                               uint32_t tag_bits, const uint64_t *alice_tags, uint64_t *tags_out,
+                               uint8_t *verified, void *stream);
+
 /* generate_random_bit_array + introduce_errors (array_and_matrix_operations.cpp:424-460)
  * for frame k seeded with seeds[k] + seed_offset (simulation.cpp:163,247),
  * on the device. alice/bob [F*N] 0/1 bytes; exact_qber[F] may be NULL.

@@ -12,6 +12,7 @@ src/array_and_matrix_operations.hpp) with batched, device-resident arrays:
   sum_product_decoding_irregular/_regular         sum_product_decoding(H, llr, syndrome, ...)
   QKD_LDPC_irregular/_regular                     qkd_ldpc(H, alice, bob, qber, ...)
   its decode step alone, Bob's side of a link      reconcile(H, bob, syndrome, qber, ...)
+  (no counterpart) key verification tags            verify_tags(H, bits, ...), reconcile(..., alice_tags=)
   generate_random_bit_array + introduce_errors    keygen(H, seeds, q_nominal, ...)
   run_trial over a batch + the batch reduction    run_trials(H, seeds, q_nominal, ...)
   seeds of QKD_LDPC_batch_simulation              make_seeds(simulation_seed, count)
@@ -42,6 +43,7 @@ __all__ = [
     "QKD_LDPC_irregular", "QKD_LDPC_regular", "keygen", "run_trials", "make_seeds",
     "qber_range", "Workspace", "counters_to_stats", "decoder_flags", "trace_decode", "set_debug_option",
     "spec_replays", "check_lanes", "interactive_simulation", "reconcile", "ReconcileResult",
+    "verify_key_words", "verify_expand_key", "verify_tags",
 ]
 
 
@@ -346,18 +348,30 @@ class ReconcileResult:
     syndromes_match: "torch.Tensor"
     bits: "torch.Tensor"
     corrected: "torch.Tensor | None"
+    # key verification (reconcile with any of its hash arguments): the corrected keys'
+    # tags (int64 bit patterns) and syndromes_match & (tag == Alice's tag)
+    tags: "torch.Tensor | None" = None
+    verified: "torch.Tensor | None" = None
 
 
 def reconcile(H: HMatrix, bob, syndrome, qber: float, max_iterations: int = 50,
               msg_threshold: float = 100.0, threshold_enabled: bool = True,
               want_corrected: bool = True, workspace=None, stream=None,
               variant: str = "sp_f64", minsum_scale: float | None = None,
-              minsum_offset: float | None = None, minsum_self_correct: bool = False) -> ReconcileResult:
+              minsum_offset: float | None = None, minsum_self_correct: bool = False,
+              hash_seed: int | None = None, hash_words=None, tag_bits: int = 64, alice_tags=None,
+              want_tags: bool = False) -> ReconcileResult:
     """Bob's side of one-way reconciliation (qkd_reconcile_batch): the decode step of
     QKD_LDPC_irregular/_regular (qkd_ldpc_algorithm.cpp:398-431) with the target syndrome
     received from Alice (her half is calculate_syndrome on her key) instead of computed
     from her key. bob [F, N] uint8 (0/1), syndrome [F, M] uint8 (nonzero = 1); one QBER
-    for the batch. bits: the last hard decision; corrected: popcount(bits ^ bob)."""
+    for the batch. bits: the last hard decision; corrected: popcount(bits ^ bob).
+
+    Key verification (qkd_reconcile_verify_batch), with any of hash_seed, hash_words,
+    alice_tags, want_tags given: tags = verify_tags of the corrected keys, from the kernel
+    that writes them; with alice_tags [F] (Alice's verify_tags under the same hash),
+    verified = syndromes_match & (tag == alice_tags) over the low tag_bits bits. Every
+    other field is what the call without them returns."""
     _need_cuda(bob, torch.uint8, "bob", H)
     _need_cuda(syndrome, torch.uint8, "syndrome", H)
     f = _frames(bob, H.num_bit_nodes, "bob")
@@ -368,10 +382,70 @@ def reconcile(H: HMatrix, bob, syndrome, qber: float, max_iterations: int = 50,
     ok = torch.empty(f, dtype=torch.uint8, device=dev)
     corrected = torch.empty(f, dtype=torch.int32, device=dev) if want_corrected else None
     flags = decoder_flags(threshold_enabled, variant, minsum_scale, minsum_offset, minsum_self_correct)
+    if hash_seed is not None or hash_words is not None or alice_tags is not None or want_tags:
+        seed, words = _verify_key(H, hash_seed, hash_words)
+        if alice_tags is not None:
+            _need_tags(alice_tags, f, "alice_tags", H)
+        # (the tags are returned whenever verification runs: 8 bytes a frame)
+        tags = torch.empty(f, dtype=torch.int64, device=dev)
+        verified = torch.empty(f, dtype=torch.uint8, device=dev) if alice_tags is not None else None
+        N.check(N.lib().qkd_reconcile_verify_batch(
+            H.handle, _ws(workspace), _ptr(bob), _ptr(syndrome), f, qber, max_iterations, msg_threshold, flags,
+            _ptr(bits), _ptr(iters), _ptr(ok), _ptr(corrected), seed, _ptr(words), tag_bits, _ptr(alice_tags),
+            _ptr(tags), _ptr(verified), _stream(stream, H.device)))
+        return ReconcileResult(iters, ok, bits, corrected, tags, verified)
     N.check(N.lib().qkd_reconcile_batch(H.handle, _ws(workspace), _ptr(bob), _ptr(syndrome), f, qber,
                                         max_iterations, msg_threshold, flags, _ptr(bits), _ptr(iters),
                                         _ptr(ok), _ptr(corrected), _stream(stream, H.device)))
     return ReconcileResult(iters, ok, bits, corrected)
+
+
+def verify_key_words(n_bits: int) -> int:
+    """W = ceil((N + 63) / 64): the 64-bit words of the verification hash's key string
+    for an N-bit key (qkd_verify_key_words)."""
+    return int(N.lib().qkd_verify_key_words(n_bits))
+
+
+def verify_expand_key(hash_seed: int, n_bits: int) -> np.ndarray:
+    """The W words the seeded form of the hash uses (qkd_verify_expand_key; SplitMix64 in
+    counter form), as a numpy uint64 array: to inspect, or to upload as hash_words."""
+    out = np.zeros(max(verify_key_words(n_bits), 1), np.uint64)
+    N.check(N.lib().qkd_verify_expand_key(hash_seed & (2**64 - 1), n_bits, out.ctypes.data))
+    return out[:verify_key_words(n_bits)]
+
+
+def _tag_dtypes():
+    return tuple(d for d in (torch.int64, getattr(torch, "uint64", None)) if d is not None)
+
+
+def _need_tags(t, count: int, name: str, H: HMatrix):
+    """A contiguous device tensor of count 64-bit words (int64 bit patterns or uint64)."""
+    if not (isinstance(t, torch.Tensor) and t.dtype in _tag_dtypes()):
+        raise QkdError(N.ERR_INVALID_ARG, f"{name} must be a contiguous int64 or uint64 CUDA tensor")
+    _need_vec(t, t.dtype, count, name, H)
+
+
+def _verify_key(H: HMatrix, hash_seed, hash_words):
+    """(seed, words) of the hash's key string: the caller's device words, or the seed."""
+    if hash_words is not None:
+        _need_tags(hash_words, verify_key_words(H.num_bit_nodes), "hash_words", H)
+    return (0 if hash_seed is None else int(hash_seed)) & (2**64 - 1), hash_words
+
+
+def verify_tags(H: HMatrix, bits, hash_seed: int = 0, hash_words=None, tag_bits: int = 64, stream=None):
+    """Key verification tags of byte keys (qkd_verify_tags_batch), Alice's half of the
+    check that follows error correction: tags[f] = the Hankel-matrix universal hash of
+    bits[f] ([F, N] uint8, a key bit is byte & 1), low tag_bits bits, as int64 bit
+    patterns. The key string is hash_words (verify_key_words(N) 64-bit words on the
+    device, truly random: the 2^-tag_bits universal form) or, without them, expanded from
+    hash_seed (a computational stand-in). A tag discloses tag_bits bits of the key."""
+    _need_cuda(bits, torch.uint8, "bits", H)
+    f = _frames(bits, H.num_bit_nodes, "bits")
+    seed, words = _verify_key(H, hash_seed, hash_words)
+    tags = torch.empty(f, dtype=torch.int64, device=bits.device)
+    N.check(N.lib().qkd_verify_tags_batch(H.handle, _ptr(bits), f, seed, _ptr(words), tag_bits, _ptr(tags),
+                                          _stream(stream, H.device)))
+    return tags
 
 
 def keygen(H: HMatrix, seeds, q_nominal: float, seed_offset: int = 0, workspace=None,

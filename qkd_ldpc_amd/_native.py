@@ -66,6 +66,7 @@ EXPORTS = [
     "qkd_code_from_alist_ex", "qkd_debug_decoder_timing", "qkd_debug_bit_order",
     "qkd_counters_merge", "qkd_debug_set_option", "qkd_debug_check_lanes",
     "qkd_reconcile_batch",
+    "qkd_verify_key_words", "qkd_verify_expand_key", "qkd_verify_tags_batch", "qkd_reconcile_verify_batch",
 ]
 
 
@@ -123,6 +124,11 @@ def lib():
             "qkd_decode_batch": (st, [P, P, P, P, SZ, U32, D, U32, P, P, P, P]),
             "qkd_qkd_ldpc_batch": (st, [P, P, P, P, SZ, D, U32, D, U32, P, P, P, P, P]),
             "qkd_reconcile_batch": (st, [P, P, P, P, SZ, D, U32, D, U32, P, P, P, P, P]),
+            "qkd_reconcile_verify_batch": (st, [P, P, P, P, SZ, D, U32, D, U32, P, P, P, P,
+                                                U64, P, U32, P, P, P, P]),
+            "qkd_verify_key_words": (SZ, [I32]),
+            "qkd_verify_expand_key": (st, [U64, I32, P]),
+            "qkd_verify_tags_batch": (st, [P, P, SZ, U64, P, U32, P, P]),
             "qkd_keygen_batch": (st, [P, P, P, U64, SZ, D, P, P, P, P]),
             "qkd_trials_batch": (st, [P, P, P, U64, SZ, D, U32, D, U32, P, P, P, P, P, P]),
             "qkd_counters_batch": (st, [P, P, P, SZ, P, C.c_int, P]),

@@ -1651,9 +1651,12 @@ static qkd_status check_no_static_lds(DecodeFn fn) {
 }
 
 // corrected (qkd_reconcile_batch, or nullptr): popcount(bits_out ^ bob) per
-// frame, from the kernel that follows the decoder
+// frame, from the kernel that follows the decoder. verify
+// (qkd_reconcile_verify_batch, or nullptr): the frames' verification tags, from
+// that kernel too.
 static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs& a, int mode,
-                                uint32_t flags, hipStream_t stream, uint32_t* corrected = nullptr) {
+                                uint32_t flags, hipStream_t stream, uint32_t* corrected = nullptr,
+                                const VerifyArgs* verify = nullptr) {
     int dc = 0;
     int rule = rule_of(flags);
     // QKD_MINSUM_STORE=global keeps the global-message-store min-sum (tests)
@@ -1975,7 +1978,7 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
                 hipLaunchKernelGGL(sfn, dim3(grid), dim3(kDecodeBlock), L.bytes, stream, a);
                 QKD_HIP(decoder_event_close(ws, stream, hipGetLastError()));
             }
-            if (mode == kModeKeys) QKD_HIP(launch_key_match(a, stream, corrected));
+            if (mode == kModeKeys) QKD_HIP(launch_key_match(a, stream, corrected, verify));
             return QKD_OK;
         }
     }
@@ -2016,6 +2019,7 @@ classic_path:
     QKD_HIP(decoder_event_close(ws, stream, hipGetLastError()));
     // (the classic kernel wrote bits_out itself)
     if (corrected) QKD_HIP(launch_count_flips(a.bits_out, a.bob_b, (uint32_t)c->n, a.n_frames, corrected, stream));
+    if (verify) QKD_HIP(launch_verify_tags(a.bits_out, (uint32_t)c->n, a.n_frames, *verify, stream));
     return QKD_OK;
 }
 
@@ -2139,12 +2143,13 @@ static SpecClean& spec_clean_of(qkd_workspace* ws, double q) {
 // Shared by qkd_qkd_ldpc_batch, qkd_trials_batch and qkd_reconcile_batch: keys
 // already packed in ws, or byte keys. syn (qkd_reconcile_batch): the target
 // syndrome given by the caller, with bob_b alone (alice_b and key_ok nullptr);
-// corrected: its flip counts.
+// corrected: its flip counts; verify (qkd_reconcile_verify_batch): its tags.
 static qkd_status decode_keys(const qkd_code* c, qkd_workspace* ws, size_t n_frames, double q,
                               uint32_t max_it, double thr, uint32_t flags, uint8_t* bits_out,
                               uint32_t* iters, uint8_t* sp_ok, uint8_t* key_ok, hipStream_t stream,
                               const uint8_t* alice_b = nullptr, const uint8_t* bob_b = nullptr,
-                              const uint8_t* syn = nullptr, uint32_t* corrected = nullptr) {
+                              const uint8_t* syn = nullptr, uint32_t* corrected = nullptr,
+                              const VerifyArgs* verify = nullptr) {
     DecodeArgs a{};
     a.alice_b = alice_b;
     a.bob_b = bob_b;
@@ -2216,7 +2221,7 @@ static qkd_status decode_keys(const qkd_code* c, qkd_workspace* ws, size_t n_fra
         a.ckpt_unsat = (uint32_t)cu;
         if (cu == 0) a.spec_cap = 0;
     }
-    qkd_status st = launch_decode(c, ws, a, kModeKeys, flags, stream, corrected);
+    qkd_status st = launch_decode(c, ws, a, kModeKeys, flags, stream, corrected, verify);
     if (st != QKD_OK || a.spec_cap == 0 || a.ckpt_unsat || ws->spec_stat_pending) return st;
     // (a QBER whose last two samples stayed under the switch is sampled again
     // only every kSpecStatEvery calls: each sample is a device-to-host copy
@@ -2263,14 +2268,12 @@ qkd_status qkd_qkd_ldpc_batch(const qkd_code* c, qkd_workspace* ws, const uint8_
                        syndromes_match, keys_match, (hipStream_t)stream, alice, bob);
 }
 
-qkd_status qkd_reconcile_batch(const qkd_code* c, qkd_workspace* ws, const uint8_t* bob,
-                               const uint8_t* syndrome, size_t n_frames, double qber, uint32_t max_iterations,
-                               double msg_threshold, uint32_t flags, uint8_t* bits_out, uint32_t* iterations,
-                               uint8_t* syndromes_match, uint32_t* corrected, void* stream) {
-    clear_error();
-    if (const char* bad = qkda::reconcile_args_error(c, bob, syndrome, n_frames, qber, bits_out, iterations,
-                                                     syndromes_match))
-        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+// qkd_reconcile_batch and qkd_reconcile_verify_batch after their argument
+// checks; verify: the second's tags, nullptr for the first.
+static qkd_status reconcile_run(const qkd_code* c, qkd_workspace* ws, const uint8_t* bob, const uint8_t* syndrome,
+                                size_t n_frames, double qber, uint32_t max_iterations, double msg_threshold,
+                                uint32_t flags, uint8_t* bits_out, uint32_t* iterations, uint8_t* syndromes_match,
+                                uint32_t* corrected, const VerifyArgs* verify, void* stream) {
     qkd_status s = check_decode_params(max_iterations, msg_threshold, flags);
     if (s != QKD_OK) return s;
     DeviceGuard g(c->device);
@@ -2283,7 +2286,63 @@ qkd_status qkd_reconcile_batch(const qkd_code* c, qkd_workspace* ws, const uint8
     // interleaved long-code decoder, which has no decisions to give, is
     // excluded by bits_out; codes it alone takes run the classic kernel)
     return decode_keys(c, ws, n_frames, qber, max_iterations, msg_threshold, flags, bits_out, iterations,
-                       syndromes_match, nullptr, (hipStream_t)stream, nullptr, bob, syndrome, corrected);
+                       syndromes_match, nullptr, (hipStream_t)stream, nullptr, bob, syndrome, corrected, verify);
+}
+
+qkd_status qkd_reconcile_batch(const qkd_code* c, qkd_workspace* ws, const uint8_t* bob,
+                               const uint8_t* syndrome, size_t n_frames, double qber, uint32_t max_iterations,
+                               double msg_threshold, uint32_t flags, uint8_t* bits_out, uint32_t* iterations,
+                               uint8_t* syndromes_match, uint32_t* corrected, void* stream) {
+    clear_error();
+    if (const char* bad = qkda::reconcile_args_error(c, bob, syndrome, n_frames, qber, bits_out, iterations,
+                                                     syndromes_match))
+        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    return reconcile_run(c, ws, bob, syndrome, n_frames, qber, max_iterations, msg_threshold, flags, bits_out,
+                         iterations, syndromes_match, corrected, nullptr, stream);
+}
+
+static VerifyArgs verify_args(const qkd_code* c, uint64_t hash_seed, const uint64_t* hash_words, uint32_t tag_bits,
+                              const uint64_t* alice_tags, uint64_t* tags_out, uint8_t* verified,
+                              const uint8_t* sp_ok) {
+    VerifyArgs v{};
+    v.seed = hash_seed;
+    v.words = hash_words;
+    v.key_words = (uint32_t)qkdv::verify_key_words(c->n);
+    v.mask = qkdv::verify_tag_mask(tag_bits);
+    v.alice_tags = alice_tags;
+    v.tags_out = tags_out;
+    v.verified = verified;
+    v.sp_ok = sp_ok;
+    return v;
+}
+
+qkd_status qkd_reconcile_verify_batch(const qkd_code* c, qkd_workspace* ws, const uint8_t* bob,
+                                      const uint8_t* syndrome, size_t n_frames, double qber,
+                                      uint32_t max_iterations, double msg_threshold, uint32_t flags,
+                                      uint8_t* bits_out, uint32_t* iterations, uint8_t* syndromes_match,
+                                      uint32_t* corrected, uint64_t hash_seed, const uint64_t* hash_words,
+                                      uint32_t tag_bits, const uint64_t* alice_tags, uint64_t* tags_out,
+                                      uint8_t* verified, void* stream) {
+    clear_error();
+    const char* bad = qkda::reconcile_args_error(c, bob, syndrome, n_frames, qber, bits_out, iterations,
+                                                 syndromes_match);
+    if (!bad) bad = qkda::reconcile_verify_args_error(tag_bits, alice_tags, tags_out, verified);
+    if (bad) return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    const VerifyArgs v = verify_args(c, hash_seed, hash_words, tag_bits, alice_tags, tags_out, verified,
+                                     syndromes_match);
+    return reconcile_run(c, ws, bob, syndrome, n_frames, qber, max_iterations, msg_threshold, flags, bits_out,
+                         iterations, syndromes_match, corrected, &v, stream);
+}
+
+qkd_status qkd_verify_tags_batch(const qkd_code* c, const uint8_t* bits, size_t n_frames, uint64_t hash_seed,
+                                 const uint64_t* hash_words, uint32_t tag_bits, uint64_t* tags, void* stream) {
+    clear_error();
+    if (const char* bad = qkda::verify_tags_args_error(c, bits, n_frames, tag_bits, tags))
+        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    DeviceGuard g(c->device);
+    const VerifyArgs v = verify_args(c, hash_seed, hash_words, tag_bits, nullptr, tags, nullptr, nullptr);
+    QKD_HIP(launch_verify_tags(bits, (uint32_t)c->n, (uint32_t)n_frames, v, (hipStream_t)stream));
+    return QKD_OK;
 }
 
 static qkd_status keygen_into_ws(const qkd_code* c, qkd_workspace* ws, const uint64_t* seeds,

@@ -2337,6 +2337,110 @@ __global__ __launch_bounds__(kCountBlock) void count_flips_kernel(const uint8_t*
     if (threadIdx.x == 0) corrected[f] = total;
 }
 
+// ---- key verification tags (qkd_verify.h) -----------------------------------
+// The frame's key string in LDS: R[0 .. key_words) from the caller's words or
+// from the seed, and a zero word after them (qkdv::verify_xor_run reads one
+// 32-bit word past its windows at every position).
+__device__ __forceinline__ void verify_stage_key(uint64_t* R, const VerifyArgs& v) {
+    for (uint32_t k = threadIdx.x; k <= v.key_words; k += kCountBlock)
+        R[k] = k == v.key_words ? 0ull : (v.words ? v.words[k] : qkdv::verify_key_word(v.seed, k));
+}
+
+// The XOR of v over the workgroup's threads, at thread 0 (red: one word per wave).
+__device__ __forceinline__ uint64_t verify_block_xor(uint64_t v, uint64_t* red) {
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        lo ^= (uint32_t)__shfl_xor((int)lo, s);
+        hi ^= (uint32_t)__shfl_xor((int)hi, s);
+    }
+    if ((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = ((uint64_t)hi << 32) | lo;
+    __syncthreads();
+    uint64_t t = 0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < kCountBlock / 64; ++w) t ^= red[w];
+    return t;
+}
+
+// Thread 0's epilogue: the masked tag out and, against Alice's, the verdict.
+__device__ __forceinline__ void verify_finish(const VerifyArgs& v, size_t f, uint64_t total) {
+    const uint64_t tag = total & v.mask;
+    if (v.tags_out) v.tags_out[f] = tag;
+    if (v.alice_tags) v.verified[f] = (v.sp_ok[f] != 0 && ((tag ^ v.alice_tags[f]) & v.mask) == 0) ? 1 : 0;
+}
+
+// The tags of byte keys (qkd_verify_tags_batch; qkd_reconcile_verify_batch
+// after the classic kernel, which wrote bits_out itself): a workgroup per
+// frame, the key string staged in LDS once, acc ^= W(p) & -(bit) over the
+// frame's positions, a block XOR, one ordinary store. No atomics. wide (the
+// host's choice: N % 8 == 0, bits 8-byte aligned): eight positions per thread
+// and pass from one 8-byte load; else a byte per thread and pass.
+__global__ __launch_bounds__(kCountBlock) void verify_tags_kernel(const uint8_t* bits, uint32_t n, uint32_t wide,
+                                                                  VerifyArgs v) {
+    extern __shared__ uint64_t vR[];
+    __shared__ uint64_t red[kCountBlock / 64];
+    const size_t f = blockIdx.x;
+    verify_stage_key(vR, v);
+    __syncthreads();
+    const uint32_t* r32 = reinterpret_cast<const uint32_t*>(vR);
+    uint64_t acc = 0;
+    if (wide) {
+        for (uint32_t i = threadIdx.x * 8; i < n; i += kCountBlock * 8)
+            acc ^= qkdv::verify_xor_run<8>(r32, i, *reinterpret_cast<const uint64_t*>(bits + f * n + i));
+    } else {
+        for (uint32_t i = threadIdx.x; i < n; i += kCountBlock) acc ^= qkdv::verify_xor_run<1>(r32, i, bits[f * n + i]);
+    }
+    const uint64_t total = verify_block_xor(acc, red);
+    if (threadIdx.x == 0) verify_finish(v, f, total);
+}
+
+// zout_unpack_count_kernel that also takes the frame's verification tag
+// (qkd_reconcile_verify_batch on the split path): the decision d at original
+// position i, already in hand for bits_out, adds W(i) & -(d) to the thread's
+// XOR; the key string sits in LDS after the decision words. corrected may be
+// nullptr: Bob's bytes are then not read at all (and quad asks nothing of
+// them).
+__global__ __launch_bounds__(kCountBlock) void zout_unpack_verify_kernel(const uint64_t* zout, const int32_t* inv,
+                                                                         uint32_t n, uint32_t words,
+                                                                         const uint8_t* bob, uint8_t* out,
+                                                                         uint32_t* corrected, uint32_t quad,
+                                                                         VerifyArgs v) {
+    extern __shared__ uint64_t zf[];          // [words] decisions, [key_words + 1] key string
+    __shared__ uint32_t red[kCountBlock / 64];
+    __shared__ uint64_t xred[kCountBlock / 64];
+    uint64_t* R = zf + words;
+    const uint32_t* r32 = reinterpret_cast<const uint32_t*>(R);
+    const size_t f = blockIdx.x;
+    for (uint32_t w = threadIdx.x; w < words; w += kCountBlock) zf[w] = zout[f * words + w];
+    verify_stage_key(R, v);
+    __syncthreads();
+    auto bit_at = [&](int32_t q) -> uint32_t { return (uint32_t)(zf[(uint32_t)q >> 6] >> ((uint32_t)q & 63u)) & 1u; };
+    uint32_t cnt = 0;
+    uint64_t acc = 0;
+    if (quad) {
+        for (uint32_t i = threadIdx.x * 4; i < n; i += kCountBlock * 4) {
+            const int4 q = *reinterpret_cast<const int4*>(inv + i);
+            const uint32_t d = bit_at(q.x) | (bit_at(q.y) << 8) | (bit_at(q.z) << 16) | (bit_at(q.w) << 24);
+            *reinterpret_cast<uint32_t*>(out + f * n + i) = d;
+            if (corrected) cnt += (uint32_t)__popc(d ^ (*reinterpret_cast<const uint32_t*>(bob + f * n + i) & 0x01010101u));
+            acc ^= qkdv::verify_xor_run<4>(r32, i, d);
+        }
+    } else {
+        for (uint32_t i = threadIdx.x; i < n; i += kCountBlock) {
+            const uint32_t d = bit_at(inv[i]);
+            out[f * n + i] = (uint8_t)d;
+            if (corrected) cnt += d ^ (uint32_t)(bob[f * n + i] & 1u);
+            acc ^= qkdv::verify_xor_run<1>(r32, i, d);
+        }
+    }
+    if (corrected) {          // (uniform over the launch)
+        const uint32_t total = count_block_sum(cnt, red);
+        if (threadIdx.x == 0) corrected[f] = total;
+    }
+    const uint64_t tag = verify_block_xor(acc, xred);
+    if (threadIdx.x == 0) verify_finish(v, f, tag);
+}
+
 // frame_syn_kernel's work bit-sliced over frames: a workgroup takes 16
 // frames and first transposes their keys into 32-bit slices T[i] (bit f =
 // Alice's bit i of frame f, bit 16 + f = Bob's; one ballot gives two bit
@@ -2608,9 +2712,18 @@ hipError_t launch_frame_syn(const DecodeArgs& a, hipStream_t stream, bool gather
     return hipGetLastError();
 }
 
-hipError_t launch_key_match(const DecodeArgs& a, hipStream_t stream, uint32_t* corrected) {
+hipError_t launch_key_match(const DecodeArgs& a, hipStream_t stream, uint32_t* corrected, const VerifyArgs* v) {
     // (decode_split_kernel compares the keys itself: keys_match needs no launch)
-    if (a.bits_out && corrected) {
+    if (a.bits_out && v) {
+        // qkd_reconcile_verify_batch: the unpack that also takes the tags (and
+        // counts the flips when asked to; Bob's bytes are read only then)
+        const uint32_t n = (uint32_t)a.code.n;
+        const bool quad = n % 4 == 0 && (((corrected ? reinterpret_cast<uintptr_t>(a.bob_b) : 0) |
+                                          reinterpret_cast<uintptr_t>(a.bits_out)) & 3u) == 0;
+        hipLaunchKernelGGL(zout_unpack_verify_kernel, dim3(a.n_frames), dim3(kCountBlock),
+                           ((size_t)a.words + v->key_words + 1) * 8, stream, a.zout, a.code.inv, n, a.words, a.bob_b,
+                           a.bits_out, corrected, quad ? 1u : 0u, *v);
+    } else if (a.bits_out && corrected) {
         // qkd_reconcile_batch: the unpack that also counts the flips against Bob's bytes
         const uint32_t n = (uint32_t)a.code.n;
         const bool quad = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(a.bob_b) |
@@ -2628,6 +2741,14 @@ hipError_t launch_key_match(const DecodeArgs& a, hipStream_t stream, uint32_t* c
 hipError_t launch_count_flips(const uint8_t* bits, const uint8_t* bob, uint32_t n, uint32_t n_frames,
                               uint32_t* corrected, hipStream_t stream) {
     hipLaunchKernelGGL(count_flips_kernel, dim3(n_frames), dim3(kCountBlock), 0, stream, bits, bob, n, corrected);
+    return hipGetLastError();
+}
+
+hipError_t launch_verify_tags(const uint8_t* bits, uint32_t n, uint32_t n_frames, const VerifyArgs& v,
+                              hipStream_t stream) {
+    const bool wide = n % 8 == 0 && (reinterpret_cast<uintptr_t>(bits) & 7u) == 0;
+    hipLaunchKernelGGL(verify_tags_kernel, dim3(n_frames), dim3(kCountBlock), ((size_t)v.key_words + 1) * 8, stream,
+                       bits, n, wide ? 1u : 0u, v);
     return hipGetLastError();
 }
 

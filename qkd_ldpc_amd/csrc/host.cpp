@@ -14,6 +14,7 @@
 #include "qkd_internal.h"
 #include "qkd_plan.h"
 #include "qkd_rng.h"
+#include "qkd_verify.h"
 
 namespace qkd {
 
@@ -831,6 +832,17 @@ qkd_status qkd_make_seeds(uint64_t simulation_seed, size_t count, uint64_t* seed
     qkdr::Xoshiro256pp g;
     g.seed(simulation_seed);
     for (size_t i = 0; i < count; ++i) seeds[i] = g.next();
+    return QKD_OK;
+}
+
+size_t qkd_verify_key_words(int32_t n_bits) { return qkdv::verify_key_words(n_bits); }
+
+qkd_status qkd_verify_expand_key(uint64_t hash_seed, int32_t n_bits, uint64_t* words_host) {
+    clear_error();
+    if (!words_host) return set_error(QKD_ERR_INVALID_ARG, "null argument");
+    if (n_bits < 1) return set_error(QKD_ERR_INVALID_ARG, "n_bits must be > 0");
+    const size_t w = qkdv::verify_key_words(n_bits);
+    for (size_t k = 0; k < w; ++k) words_host[k] = qkdv::verify_key_word(hash_seed, k);
     return QKD_OK;
 }
 

@@ -1,6 +1,6 @@
 // qkd_args.h — host-only argument checks of the batched entry points, free of
 // HIP so that a stand-alone host program can exercise them
-// (tests/native/reconcile_args_check.cpp).
+// (tests/native/reconcile_args_check.cpp, tests/native/verify_hash_check.cpp).
 #pragma once
 
 #include <stddef.h>
@@ -20,6 +20,29 @@ inline const char* reconcile_args_error(const void* code, const uint8_t* bob, co
     if (n_frames == 0) return "n_frames must be > 0";
     if (n_frames > 0xffffffffull) return "n_frames too large";
     if (!(qber > 0.0 && qber < 1.0)) return "QBER must be in (0,1)";
+    return nullptr;
+}
+
+// qkd_verify_tags_batch's arguments, the same way. hash_words may be NULL
+// (the seeded key string) and is not looked at.
+inline const char* verify_tags_args_error(const void* code, const uint8_t* bits, size_t n_frames, uint32_t tag_bits,
+                                          const uint64_t* tags) {
+    if (!code || !bits || !tags) return "null argument";
+    if (n_frames == 0) return "n_frames must be > 0";
+    if (n_frames > 0xffffffffull) return "n_frames too large";
+    if (tag_bits < 1 || tag_bits > 64) return "tag_bits must be in 1..64";
+    return nullptr;
+}
+
+// What qkd_reconcile_verify_batch adds to qkd_reconcile_batch's arguments
+// (checked after reconcile_args_error): a tag to give or a tag to compare
+// with, and verified exactly when alice_tags is given.
+inline const char* reconcile_verify_args_error(uint32_t tag_bits, const uint64_t* alice_tags,
+                                               const uint64_t* tags_out, const uint8_t* verified) {
+    if (tag_bits < 1 || tag_bits > 64) return "tag_bits must be in 1..64";
+    if (!alice_tags && !tags_out) return "neither alice_tags nor tags_out given";
+    if (alice_tags && !verified) return "alice_tags given without verified";
+    if (!alice_tags && verified) return "verified given without alice_tags";
     return nullptr;
 }
 

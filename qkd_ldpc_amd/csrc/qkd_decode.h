@@ -9,6 +9,7 @@
 #include "qkd_math.h"
 #include "qkd_plan.h"
 #include "qkd_spec.h"
+#include "qkd_verify.h"
 
 namespace qkd {
 
@@ -66,6 +67,20 @@ enum DecodeRule : int {
 };
 template <int RULE> struct RuleMsg { using T = float; };
 template <> struct RuleMsg<kRuleSp64> { using T = double; };
+
+// Key verification (qkd_verify.h) of a launch's frames: the key string, the
+// tag mask and where the tags go. verified[f] = sp_ok[f] && the masked tag
+// equals alice_tags[f]'s; written exactly when alice_tags is given.
+struct VerifyArgs {
+    uint64_t seed;                // the seeded key string (words == nullptr)
+    const uint64_t* words;        // the caller's key string (key_words of them, device) or nullptr
+    uint32_t key_words;           // qkdv::verify_key_words(n)
+    uint64_t mask;                // qkdv::verify_tag_mask(tag_bits)
+    const uint64_t* alice_tags;   // [F] or nullptr
+    uint64_t* tags_out;           // [F] or nullptr
+    uint8_t* verified;            // [F], with alice_tags
+    const uint8_t* sp_ok;         // [F] the decoder's syndromes_match, with alice_tags
+};
 
 struct DecodeArgs {
     DeviceCode code;
@@ -699,9 +714,16 @@ hipError_t launch_frame_syn(const DecodeArgs& a, hipStream_t stream, bool gather
 hipError_t launch_pack_keys(const DecodeArgs& a, hipStream_t stream);
 // corrected (qkd_reconcile_batch, with a.bits_out and a.bob_b): the unpack
 // also writes popcount(bits_out ^ bob) per frame
-hipError_t launch_key_match(const DecodeArgs& a, hipStream_t stream, uint32_t* corrected = nullptr);
+// v (qkd_reconcile_verify_batch): the unpack also takes the frame's
+// verification tag (zout_unpack_verify_kernel; corrected may then be nullptr)
+hipError_t launch_key_match(const DecodeArgs& a, hipStream_t stream, uint32_t* corrected = nullptr,
+                            const VerifyArgs* v = nullptr);
 // the same count after the classic kernel, which writes bits_out itself
 hipError_t launch_count_flips(const uint8_t* bits, const uint8_t* bob, uint32_t n, uint32_t n_frames,
                               uint32_t* corrected, hipStream_t stream);
+// the verification tags of byte keys bits[F x N] (qkd_verify_tags_batch, and
+// qkd_reconcile_verify_batch after the classic kernel): one launch, no workspace
+hipError_t launch_verify_tags(const uint8_t* bits, uint32_t n, uint32_t n_frames, const VerifyArgs& v,
+                              hipStream_t stream);
 
 }  // namespace qkd
