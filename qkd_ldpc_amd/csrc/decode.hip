@@ -1605,13 +1605,24 @@ static qkd_status plan_for_layout(const qkd_code* c, const SplitLds& L, int dc, 
                 w.y = encode_seg(w.y & qkdp::kPlanChkMask, (w.y >> 20) & 63u, (w.y >> 26) + 1, (uint32_t)(k & 63),
                                  (uint32_t)dc);
             }
-            // per task dc rows of slot words, then the row of check words
+            // per task dc rows of slot words, then the row of check words;
+            // entries past a check's degree as the reserved dead word, which
+            // must be out of range for this layout's LDS and for the largest
+            // region of global slots a launch gives it (launch_decode: the
+            // rest rounded up to an odd multiple of kC2bPad, or padded by at
+            // most n_pad)
+            const size_t slots = (size_t)c->max_dv * c->n_pad;
+            if (!slot_dead_ok(L.bytes, slots - L.S + (size_t)c->n_pad + 2 * kC2bPad))
+                return set_error(QKD_ERR_UNSUPPORTED, "check-lane plan: the dead slot word is in range of a layout "
+                                                      "of %zu B LDS and %zu slots", L.bytes, slots);
             const size_t tasks = h.chk.size() / 64;
             std::vector<uint32_t> words(tasks * (size_t)(dc + 1) * 64);
             for (size_t t = 0; t < tasks; ++t) {
-                for (size_t k = 0; k < (size_t)dc * 64; ++k)
+                for (size_t k = 0; k < (size_t)dc * 64; ++k) {
+                    const uint32_t x = h.slot[t * (size_t)dc * 64 + k];
                     words[t * (size_t)(dc + 1) * 64 + k] =
-                        encode_slot(h.slot[t * (size_t)dc * 64 + k], L.S, (uint32_t)L.msg, (uint32_t)sizeof(double));
+                        x == qkdp::kNoSlot ? kSlotDead : encode_slot(x, L.S, (uint32_t)L.msg, (uint32_t)sizeof(double));
+                }
                 for (size_t l = 0; l < 64; ++l) words[(t * (size_t)(dc + 1) + (size_t)dc) * 64 + l] = h.chk[t * 64 + l];
             }
             words.resize((words.size() + 1) & ~(size_t)1, 0u);
@@ -1787,8 +1798,10 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
                 a.c2b_stride = st * kC2bPad;
             }
             // an encoded global slot word (kSlotGlobalBase + byte offset) must
-            // stay below kSlotLds, the LDS words' tag bit
-            if (rule == kRuleSp64 && kSlotGlobalBase + a.c2b_stride * sizeof(double) >= kSlotLds)
+            // stay below kSlotLds, the LDS words' tag bit, and the region's
+            // buffer range below the dead slot word (qkd_decode.h kSlotDead)
+            static_assert(kSlotDead < kSlotLds, "the dead word bounds the global words");
+            if (rule == kRuleSp64 && !slot_dead_ok(L.bytes, a.c2b_stride))
                 return set_error(QKD_ERR_UNSUPPORTED, "code too large for the split decoder's slot words "
                                                       "(%zu global slots per frame)", a.c2b_stride);
             a.lds_budget = (uint32_t)budget;
@@ -2568,9 +2581,10 @@ __global__ void math_kernel(int which, const double* x, double* y, size_t n) {
         }
         case 10:
         case 11: {
-            // pairs of exact b2c (x[2k], x[2k+1]) -> raw binary32 psi bounds
-            // (lo, hi of each): 10 the packed qkds::psi_of_exact2, 11 the
-            // scalar psi_of_exact twice; one thread per pair
+            // pairs of exact b2c (x[2k], x[2k+1]) -> the raw psi slots (low
+            // word: lo with the sign of b2c in bit 31, high word: hi; NaN in
+            // both: sign not certain): 10 the packed qkds::psi_of_exact2, 11
+            // the scalar psi_of_exact twice; one thread per pair
             if (i & 1) break;
             qkds::f2 r0, r1;
             if (which == 10) {

@@ -654,19 +654,20 @@ __device__ __forceinline__ void spec_check_phase_psi(const uint2* __restrict__ p
     // there: keep them finite (the prologue stages key words in this region)
     if (lane < DC) row[64 + lane] = 0.0;
     auto slot = [&](uint2 p) -> uint32_t { return pw_slot(p); };
-    // phi(|b2c|) / ln 2 with the sign of b2c in the low word, NaN when the
-    // sign is not certain (psi_of_exact); idle lanes (the dummy column) do
-    // not count. The row entry is the magnitude's bounds (0 when uncertain).
+    // phi(|b2c|) / ln 2 with the sign of b2c in bit 31 of the low word, NaN
+    // when the sign is not certain (psi_of_exact's sign-magnitude slots); idle
+    // lanes (the dummy column) do not count. The row entry is the magnitude's
+    // bounds.
     auto input = [&](double xv, uint2 w, bool& neg) -> f2 {
         const f2 bv = qkds::unpack_iv(xv);
-        neg = bv.x < 0.0f;
+        neg = (int32_t)__builtin_bit_cast(uint32_t, bv.x) < 0;
         const bool ok = bv.x == bv.x;
         // (an uncertain entry stays NaN in the row: the round aborts on it, so
         // what it does to the other lanes' sums never stands; the dummy
         // column's entry is finite. Two ballots of plain compares: a ballot of
         // their conjunction materialises it as 0 / 1 and compares it back)
         bad |= fold64(__ballot(!ok) & __ballot(pw_slot(w) != dummy));
-        return neg_iv_if(neg, bv);
+        return qkds::psi_slot_mag(bv);
     };
     uint2 wt = plan_word(prs, t, lane);
     uint2 wn = plan_word(prs, t + NW, lane);
@@ -831,15 +832,29 @@ __device__ __forceinline__ void spec_check_phase_paired(const uint2* __restrict_
 // The same check phases with one CHECK per lane (the check-lane plan,
 // qkd_plan.h CheckLanePlan; buckets 4 and 6): a lane loads its check's DC
 // slots, forms every extrinsic sum in registers as a prefix plus a suffix sum
-// and writes the DC messages back -- no row buffer, no cross-lane step, the
-// parity a popcount of in-register sign bits, and DC / 2 independent packed
-// phi evaluations in flight per lane (the rule of decode_ilv.hip's check
-// phase, parity-tested since the interleaved decoder).
-// Entries past the check's degree read and write the dummy column's slot and
-// count as exact zeros; lanes without a check (degree 0) are all dead.
+// and writes the DC messages back -- no row buffer, no cross-lane step, and
+// DC / 2 independent packed phi evaluations in flight per lane (the rule of
+// decode_ilv.hip's check phase, parity-tested since the interleaved decoder).
+// Entries past the check's degree carry the reserved slot word kSlotDead, out
+// of range for both halves of an access: they load {+0, +0} and their stores
+// are dropped; lanes without a check (degree 0) are all dead.
 // PSI_IN: the slots hold the psi bounds of exact b2c (iteration 2 after the
-// folded first one, psi_of_exact: the sign in the low word, NaN = uncertain);
-// otherwise b2c intervals, bounded two edges per packed call (phi_bounds2).
+// folded first one, psi_of_exact: sign-magnitude, NaN = uncertain), so a dead
+// entry reads as "psi = 0, sign +" and needs no select at all; otherwise b2c
+// intervals, bounded two edges per packed call (phi_bounds2), where phi of a
+// dead entry's 0 is not 0 and one select per entry zeroes it.
+// Signs: the XOR of the entries' raw sign words (the psi slot's low word, the
+// b2c interval's high word) and the target bit moved to bit 31 is the check's
+// parity in bit 31; entry k's sigma is that XOR its own word (the other bits
+// are garbage and ignored).
+// Certification: the lanes that cannot certify are kept as a wave mask
+// (v_cmp results ORed in scalar registers, no per-lane flag). A live b2c
+// interval must exceed 1e-30 in magnitude (an explicit compare per entry:
+// a positive bound under 1e-30 gives a finite psi). In the psi-input form an
+// uncertain entry is NaN and reaches the sum of all entries; finite inputs
+// cannot reach kPsiSumMax (DC <= 8 terms of at most psi(1e-30) < 101 each), so
+// one test of that total per check, !(total < kPsiSumMax), replaces the tests
+// of every entry and of every extrinsic sum.
 // Any edge order gives an enclosing interval: the sums of DC - 1 terms are
 // widened by (DC + 2) kSumRel relative and kRefSumAbs absolute, as the
 // edge-lane phases charge theirs.
@@ -878,44 +893,45 @@ __device__ __forceinline__ void spec_check_phase_lanes(const uint32_t* __restric
         for (int k = 0; k < DC; ++k) w.s[k] = *reinterpret_cast<const uint32_t*>(base + k * 256 + vlane);
         w.c = *reinterpret_cast<const uint32_t*>(base + DC * 256 + vlane);
     };
-    bool bad = false;       // a live entry that could not certify (a lane mask: scalar ors)
+    uint64_t badm = 0;      // the lanes with a live entry that could not certify
     auto step = [&](const Words& w_t, Words& w_n) -> bool {
         typedef __attribute__((address_space(3))) const uint32_t LdsU32;
         SplitStore<double>::Raw x[DC];
 #pragma unroll
         for (int k = 0; k < DC; ++k) x[k] = ms.ld_raw(w_t.s[k]);
         const uint32_t sword = *reinterpret_cast<LdsU32*>((size_t)qkdp::chk_word_addr(w_t.c));
-        const int deg = (int)qkdp::chk_word_deg(w_t.c);
-        // psi bounds of |b2c| per entry (exact zeros for dead ones) and the signs
+        // psi bounds of |b2c| per entry (exact zeros for dead ones), the raw
+        // sign words and their XOR
         f2 ph[DC];
-        uint32_t negs = 0;
+        uint32_t sw[DC], sx = 0;
 #pragma unroll
         for (int k = 0; k < DC; k += 2) {
             const f2 b0 = qkds::unpack_iv(ms.pick(x[k])), b1 = qkds::unpack_iv(ms.pick(x[k + 1]));
-            const bool in0 = k < deg, in1 = k + 1 < deg;
-            bool n0, n1, ok0, ok1;
-            f2 r0, r1;
             if constexpr (PSI_IN) {
-                n0 = b0.x < 0.0f;
-                n1 = b1.x < 0.0f;
-                ok0 = b0.x == b0.x;
-                ok1 = b1.x == b1.x;
-                r0 = neg_iv_if(n0, b0);
-                r1 = neg_iv_if(n1, b1);
+                sw[k] = __builtin_bit_cast(uint32_t, b0.x);
+                sw[k + 1] = __builtin_bit_cast(uint32_t, b1.x);
+                ph[k] = qkds::psi_slot_mag(b0);
+                ph[k + 1] = qkds::psi_slot_mag(b1);
             } else {
-                n0 = b0.y < 0.0f;
-                n1 = b1.y < 0.0f;
-                const f2 a0 = neg_iv_if(n0, b0), a1 = neg_iv_if(n1, b1);
-                // certified: the interval excludes 0 by a margin (spec_check_phase_paired)
-                ok0 = a0.x > 1.0e-30f;
-                ok1 = a1.x > 1.0e-30f;
+                const int deg = (int)qkdp::chk_word_deg(w_t.c);
+                const bool in0 = k < deg, in1 = k + 1 < deg;
+                sw[k] = __builtin_bit_cast(uint32_t, b0.y);
+                sw[k + 1] = __builtin_bit_cast(uint32_t, b1.y);
+                // (a certified interval's high bound is neither 0 nor NaN: the
+                // compare and the raw word's bit 31 agree on its sign)
+                const f2 a0 = neg_iv_if(b0.y < 0.0f, b0), a1 = neg_iv_if(b1.y < 0.0f, b1);
+                // certified: the interval excludes 0 by a margin
+                // (spec_check_phase_paired; two ballots of plain compares each)
+                badm |= __ballot(!(a0.x > 1.0e-30f)) & __ballot(in0);
+                badm |= __ballot(!(a1.x > 1.0e-30f)) & __ballot(in1);
+                f2 r0, r1;
                 qkds::phi_bounds2(a0, a1, r0, r1);
+                // (an uncertified live entry's bounds stay as they came out:
+                // the round aborts)
+                ph[k] = in0 ? r0 : f2{0.0f, 0.0f};
+                ph[k + 1] = in1 ? r1 : f2{0.0f, 0.0f};
             }
-            bad |= (in0 && !ok0) || (in1 && !ok1);
-            negs |= (in0 && n0 ? 1u : 0u) << k;
-            negs |= (in1 && n1 ? 1u : 0u) << (k + 1);
-            ph[k] = (in0 && ok0) ? r0 : f2{0.0f, 0.0f};
-            ph[k + 1] = (in1 && ok1) ? r1 : f2{0.0f, 0.0f};
+            sx ^= sw[k] ^ sw[k + 1];
             // (one pair at a time: the scheduler otherwise interleaves all DC / 2
             // evaluations, and their temporaries push the kernel's long-lived
             // values into scratch)
@@ -926,8 +942,11 @@ __device__ __forceinline__ void spec_check_phase_lanes(const uint32_t* __restric
         __builtin_amdgcn_sched_barrier(0);
         load_words(t + NW, w_n);
         __builtin_amdgcn_sched_barrier(0);
-        // sigma of entry k = s_j ^ parity of the signs ^ its own
-        const uint32_t sp = ((sword >> qkdp::chk_word_bit(w_t.c)) + (uint32_t)__popc(negs)) & 1u;
+        // sigma of entry k = s_j ^ parity of the signs ^ its own, in bit 31:
+        // the target bit moved there (31 - its position is the low five bits
+        // of the check word's complement, all a shift takes)
+        static_assert(qkdp::chk_word_bit(~0u) == 31u, "the bit position: the check word's low five bits");
+        const uint32_t sp = sx ^ (sword << (~w_t.c & 31u));
         // extrinsic sums by pairs: entry k of pair i sums the pair's other
         // entry and the other pairs (a prefix and a suffix over the pair
         // sums; every term >= 0, at most DC - 2 additions per sum)
@@ -942,6 +961,10 @@ __device__ __forceinline__ void spec_check_phase_lanes(const uint32_t* __restric
                 oth[i] = pre;
                 pre = pre + pp[i];
             }
+            // the sum of every entry: NaN (or inf) if any live input is -- the
+            // one certification test of the psi-input form; finite inputs stay
+            // under DC psi(1e-30) < kPsiSumMax, and so does every extrinsic sum
+            badm |= __ballot(!(pre.y < qkds::kPsiSumMax));
             f2 suf = pp[HP - 1];
 #pragma unroll
             for (int i = HP - 2; i >= 0; --i) {
@@ -954,7 +977,6 @@ __device__ __forceinline__ void spec_check_phase_lanes(const uint32_t* __restric
             const float mg = __builtin_fmaf(sum.y, (float)(DC + 2) * qkds::kSumRel, qkds::kRefSumAbs);
             f2 e = sum + f2{-mg, mg};
             e.x = e.x > 0.0f ? e.x : 0.0f;
-            bad |= k < deg && !(e.y < qkds::kPsiSumMax);      // the reference's product would underflow
             return e;
         };
         // the c2b bounds two entries per packed evaluation, descending, each
@@ -970,10 +992,8 @@ __device__ __forceinline__ void spec_check_phase_lanes(const uint32_t* __restric
             m0.y = __builtin_amdgcn_fmed3f(m0.y, 0.0f, thr_up);
             m1.x = __builtin_amdgcn_fmed3f(m1.x, 0.0f, thr_dn);
             m1.y = __builtin_amdgcn_fmed3f(m1.y, 0.0f, thr_up);
-            const uint32_t s0 = (sp ^ (negs >> (k - 1))) & 1u;
-            const uint32_t s1 = (sp ^ (negs >> k)) & 1u;
-            ms.st_w(w_t.s[k - 1], qkds::pack_iv(neg_iv_if(s0 != 0u, m0)));
-            ms.st_w(w_t.s[k], qkds::pack_iv(neg_iv_if(s1 != 0u, m1)));
+            ms.st_w(w_t.s[k - 1], qkds::pack_iv(neg_iv_if((int32_t)(sp ^ sw[k - 1]) < 0, m0)));
+            ms.st_w(w_t.s[k], qkds::pack_iv(neg_iv_if((int32_t)(sp ^ sw[k]) < 0, m1)));
             __builtin_amdgcn_sched_barrier(0);
         }
         t = __builtin_amdgcn_readfirstlane(t + NW);
@@ -985,7 +1005,7 @@ __device__ __forceinline__ void spec_check_phase_lanes(const uint32_t* __restric
         if (!step(wa, wb)) break;
         if (!step(wb, wa)) break;
     }
-    if (fold64(__ballot(bad)) != 0 && lane == 0) atomicOr(round_word, 2u);
+    if (fold64(badm) != 0 && lane == 0) atomicOr(round_word, 2u);
 }
 
 // The folded first iteration as a table (speculative kernel, QKD path): its

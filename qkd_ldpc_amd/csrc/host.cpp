@@ -495,7 +495,7 @@ static qkd_status build_code(qkd_code* c, int32_t n, int32_t m, const int32_t* c
                 h.rem_tasks = cl.rem.n_tasks;
                 h.slot.resize(cl.edge.size());
                 for (size_t k = 0; k < cl.edge.size(); ++k)
-                    h.slot[k] = cl.edge[k] < 0 ? (uint32_t)n : (uint32_t)slot_of[cl.edge[k]];
+                    h.slot[k] = cl.edge[k] < 0 ? qkdp::kNoSlot : (uint32_t)slot_of[cl.edge[k]];
                 h.chk = cl.chkw;
                 h.rem.resize(cl.rem.word.size());
                 for (size_t k = 0; k < cl.rem.word.size(); ++k) {

@@ -655,6 +655,21 @@ constexpr uint32_t kSlotGlobalBase = 0x40000u;
 __host__ __device__ inline uint32_t encode_slot(uint32_t x, uint32_t S, uint32_t msg, uint32_t esz) {
     return x < S ? (kSlotLds | (msg + x * esz)) : (kSlotGlobalBase + (x - S) * esz);
 }
+// The reserved word of a slot that does not exist (the check-lane plan's
+// entries past a check's degree): out of range for BOTH halves of an access,
+// so it loads 0 and its store goes nowhere. As an LDS address it is past any
+// allocation in the way every global word is, whatever number of low address
+// bits the hardware compares (all of them are set); as a buffer offset it is
+// past the descriptor's range as long as the range ends at or below it.
+// slot_dead_ok says so for an LDS allocation and a region of global slots (8
+// bytes each): plan_for_layout checks every layout it encodes against the
+// largest region a launch can give it, launch_decode the region it gives.
+// 8-byte aligned, as every slot word.
+constexpr uint32_t kSlotDead = 0x7ffffff8u;
+static_assert((kSlotDead & (kSlotLds | 7u)) == 0, "a global-form word, aligned");
+__host__ __device__ inline bool slot_dead_ok(size_t lds_bytes, size_t global_slots) {
+    return lds_bytes <= kSlotGlobalBase && (size_t)kSlotGlobalBase + global_slots * 8 <= kSlotDead;
+}
 
 // The encoded plan's second word (check-degree bucket DC), the lane's
 // segment and its check's target bit pre-decoded for the check phases:
@@ -676,8 +691,10 @@ __host__ __device__ inline uint32_t encode_seg(uint32_t j, uint32_t start, uint3
 
 // The check-lane plan (qkd_plan.h CheckLanePlan) encoded for a layout: per
 // task dc + 1 rows of 64 words, one per lane: rows k < dc the encoded slot
-// word (encode_slot) of the lane's check's k-th entry (the dummy column's past
-// its degree), row dc the check's word as the plan builder made it
+// word (encode_slot) of the lane's check's k-th entry (past its degree the
+// reserved word kSlotDead: the entry loads {+0, +0}, which the psi-input form
+// reads as "psi = 0, sign +", and its store is dropped -- no compare with the
+// degree on its account), row dc the check's word as the plan builder made it
 // (qkdp::encode_chk: syndrome word offset, bit, degree).
 // In DecodeArgs::plan_enc the remainder's edge-lane plan (rem_tasks +
 // kPlanPadTasks tasks) follows the n_tasks + kPlanPadTasks tasks of the whole

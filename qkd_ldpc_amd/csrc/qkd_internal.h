@@ -233,7 +233,7 @@ struct qkd_code {
     // bit_code), slot-addressed on the host: [0] the split form (whole rounds
     // of check-lane tasks plus an edge-lane remainder), [1] the pure form
     // (every check on a lane; A/B runs). slot: (cl_tasks + pad) * cl_dc * 64
-    // slot indices (the dummy column's for dead entries); chk: the lanes'
+    // slot indices (qkdp::kNoSlot for dead entries); chk: the lanes'
     // check words as the builder made them (qkdp::encode_chk; 0: none); rem:
     // the remainder's plan in plan_slot_host's form
     struct ClHost {

@@ -153,9 +153,11 @@ inline bool build_wave_plan(int32_t n, int32_t m, const int32_t* cptr, const int
 // run one CHECK per lane instead: task T, lane l holds check chk[T * 64 + l]
 // and its dc entries edge[(T * dc + k) * 64 + l], k < dc (k-major across the
 // lanes: each of a task's dc loads is coalesced). Entries k >= the check's
-// degree are dead (-1): the kernels point them at the dummy column's slot and
-// give them weight 0. Lanes without a check (the last task's tail and the
-// kPlanPadTasks pad tasks) have chk = -1 and every entry dead.
+// degree are dead (-1): they have no slot (kNoSlot once the host addresses the
+// plan by slots; encoded for a layout, the reserved word kSlotDead of
+// qkd_decode.h, which loads 0 and stores nowhere). Lanes without a check (the
+// last task's tail and the kPlanPadTasks pad tasks) have chk = -1 and every
+// entry dead.
 //
 // Split rule (pure = false): the check-lane part takes whole rounds of
 // round_tasks wave tasks (one per wave of the workgroup), i.e. the first
@@ -175,6 +177,7 @@ inline bool build_wave_plan(int32_t n, int32_t m, const int32_t* cptr, const int
 //   bits 19-31  (j >> 5) * 4: the byte offset of the check's syndrome word
 //               (the split kernels' syndrome words lead their LDS; M <= 65536)
 constexpr uint32_t kChkDegShift = 5, kChkWordShift = 19;
+constexpr uint32_t kNoSlot = 0xffffffffu;     // the slot index of a dead entry
 constexpr uint32_t encode_chk(uint32_t j, uint32_t deg) {
     return (j & 31u) | (deg << kChkDegShift) | (((j >> 5) * 4u) << kChkWordShift);
 }

@@ -255,16 +255,27 @@ __device__ __forceinline__ f2 iv_of(double x) {
 // The folded first bit phase's b2c are exact binary64 values: it stores, in
 // place of their intervals, the psi bounds the next check phase would compute
 // from those intervals (bit for bit the same), with the sign of b2c carried by
-// the low word: [lo, hi] for b2c > 0, [-hi, -lo] for b2c < 0 (hi > 0, so the
-// low word is negative exactly then); NaN for a b2c whose sign is not certain
-// (0 or NaN: the check phase aborts the round).
+// the low word in sign-magnitude form: [lo | sign << 31, hi], sign = b2c < 0
+// (lo >= +0 always -- phi_bounds floors it at +0 -- so its sign bit is free:
+// a reader's magnitude is the low word without bit 31, psi_slot_mag, and the
+// sign of b2c is bit 31 of the raw word, which the check phases XOR into the
+// check's parity as it is); NaN in both words for a b2c whose sign is not
+// certain (0 or NaN: the check phase aborts the round).
+constexpr uint32_t kSignBit = 0x80000000u;
+__device__ __forceinline__ f2 psi_slot(bool ok, bool neg, f2 ph) {
+    const float lo = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, ph.x) | (neg ? kSignBit : 0u));
+    return ok ? f2{lo, ph.y} : f2{__builtin_nanf(""), __builtin_nanf("")};
+}
+// a psi slot's magnitude bounds (NaN stays NaN)
+__device__ __forceinline__ f2 psi_slot_mag(f2 v) {
+    return f2{__builtin_bit_cast(float, __builtin_bit_cast(uint32_t, v.x) & ~kSignBit), v.y};
+}
 __device__ __forceinline__ f2 psi_of_exact(double b) {
     const f2 iv = iv_of(b);
     const bool neg = iv.y < 0.0f;
     const f2 ab = neg ? -iv.yx : iv;
     const bool ok = (neg || iv.x > 0.0f) && ab.x > 1.0e-30f;
-    const f2 ph = phi_bounds(ab.x, ab.y);
-    return ok ? (neg ? -ph.yx : ph) : f2{__builtin_nanf(""), __builtin_nanf("")};
+    return psi_slot(ok, neg, phi_bounds(ab.x, ab.y));
 }
 
 // psi_of_exact of two values in one packed evaluation (phi_bounds' operations
@@ -288,9 +299,8 @@ __device__ __forceinline__ void psi_of_exact2(double b0, double b1, f2& r0, f2& 
     const f2 t = __builtin_elementwise_fma(-e.slope * f2((1.0f + 2.0f * kPhiRel) * kInvLn2), f2{a0.y, a1.y} - x,
                                            e.v * f2(1.0f - kPhiRel));
     const f2 ph0 = f2{t.x > 0.0f ? t.x : 0.0f, hi.x}, ph1 = f2{t.y > 0.0f ? t.y : 0.0f, hi.y};
-    const float nan = __builtin_nanf("");
-    r0 = ok0 ? (n0 ? -ph0.yx : ph0) : f2{nan, nan};
-    r1 = ok1 ? (n1 ? -ph1.yx : ph1) : f2{nan, nan};
+    r0 = psi_slot(ok0, n0, ph0);
+    r1 = psi_slot(ok1, n1, ph1);
 }
 
 // phi_bounds of two intervals [a.x, a.y] and [b.x, b.y] in one packed
