@@ -267,6 +267,64 @@ QKD_API qkd_status qkd_reconcile_verify_batch(const qkd_code *code, qkd_workspac
                                uint32_t tag_bits, const uint64_t *alice_tags, uint64_t *tags_out,
                                uint8_t *verified, void *stream);
 
+/* ---- privacy amplification --------------------------------------------------
+ * The last step before a secret key: the corrected (and verified) key is
+ * hashed down to out_bits bits with a matrix of the same Hankel family as the
+ * verification hash, only with a long output. For an input of n_in bits x_p
+ * and an output of L = out_bits bits:
+ *   out_i = XOR over the positions p with x_p = 1 of r[p + i],  0 <= i < L
+ * where r[k] = (R[k >> 6] >> (k & 63)) & 1, 0 <= k <= n_in + L - 2, is bit k of
+ * a key string R of Wp = qkd_privacy_key_words(n_in, L) =
+ * ceil((n_in + L - 1) / 64) 64-bit words. The all-zero input hashes to all
+ * zeros; an input bit is byte & 1. The output of a frame is packed into
+ * Wo = ceil(L / 64) words: bit i of frame f is
+ * (out_words[f * Wo + (i >> 6)] >> (i & 63)) & 1, and the bits at and above L
+ * of the last word are written as 0.
+ *
+ * R is the caller's hash_words[Wp] (device memory; truly random bits shared
+ * by Alice and Bob: the form for which the family is universal), or, with
+ * hash_words == NULL, expanded from hash_seed as for verification:
+ * R[k] = mix(hash_seed + (k + 1) * 0x9E3779B97F4A7C15). The seeded form is a
+ * computational stand-in, NOT an information-theoretic one: its key string has
+ * at most 64 bits of entropy.
+ *
+ * With n_in = N, L = 64 and the same key string the output word IS the 64-bit
+ * verification tag (qkd_privacy_key_words(N, 64) == qkd_verify_key_words(N)).
+ * A link must therefore NOT reuse its verification string (or seed) for
+ * privacy amplification: the announced tag would be 64 bits of the secret key.
+ * The two strings must be independent.
+ *
+ * How many bits to keep (out_bits) is the caller's protocol decision: the
+ * syndrome bits disclosed, the tag bits, the finite-key terms and the security
+ * parameter all come off there. */
+#define QKD_PRIVACY_MAX_BITS (1u << 20)   /* n_in and out_bits */
+
+/* Wp, the 64-bit words of the key string; 0 unless
+ * 1 <= out_bits <= n_in <= QKD_PRIVACY_MAX_BITS. Host only. */
+QKD_API size_t qkd_privacy_key_words(uint32_t n_in, uint32_t out_bits);
+
+/* The Wp words the seeded form uses, into host memory (to inspect them, or to
+ * upload them as hash_words). Host only, no device work. */
+QKD_API qkd_status qkd_privacy_expand_key(uint64_t hash_seed, uint32_t n_in, uint32_t out_bits,
+                                          uint64_t *words_host);
+
+/* out_words[F * Wo] = the hashes of keys[F * n_in] (0/1 bytes on `device`, only
+ * byte & 1 counts; contiguous rows, base address of any alignment). n_in is
+ * not tied to a code: to hash B consecutive corrected frames as one block pass
+ * the same buffer with n_in = B * N and n_frames = F / B. keep[F] (may be NULL;
+ * typically `verified` of qkd_reconcile_verify_batch): a frame with
+ * keep[f] == 0 gets Wo zero words, so that an unverified key never leaves as a
+ * secret key; the other frames are unaffected. out_words is fully overwritten
+ * and nothing is written outside it. QKD_ERR_INVALID_ARG, before any device
+ * work, unless 1 <= out_bits <= n_in <= QKD_PRIVACY_MAX_BITS, n_frames >= 1 and
+ * keys and out_words are given. Kernel launches on the stream only: no
+ * workspace, no allocation, no host copy, no synchronisation, no atomics (the
+ * same bits on every run); capturable in a graph. */
+QKD_API qkd_status qkd_privacy_amplify_batch(int device, const uint8_t *keys, size_t n_frames,
+                                             uint32_t n_in, uint32_t out_bits, uint64_t hash_seed,
+                                             const uint64_t *hash_words, const uint8_t *keep,
+                                             uint64_t *out_words, void *stream);
+
 /* generate_random_bit_array + introduce_errors (array_and_matrix_operations.cpp:424-460)
  * for frame k seeded with seeds[k] + seed_offset (simulation.cpp:163,247),
  * on the device. alice/bob [F*N] 0/1 bytes; exact_qber[F] may be NULL.
@@ -346,6 +404,12 @@ QKD_API qkd_status qkd_counters_merge(const qkd_counters *records, size_t n_reco
  *                              remaining checks edge per lane; 2 every check
  *                              on a lane (A/B). Chosen per launch; outputs
  *                              are the same
+ *   QKD_PRIVACY_KERNEL direct|table  (ws == NULL) the form of
+ *                              qkd_privacy_amplify_batch: one lane per output
+ *                              word, or bit-sliced over 32 frames with lookup
+ *                              tables in LDS (the default; table1 | table2 |
+ *                              table4 fix its outputs per lane, which it
+ *                              otherwise chooses from the launch's size)
  * An unknown name fails with QKD_ERR_INVALID_ARG. Thread-safe. No reference
  * counterpart (the reference's CFG fields are the decode parameters). */
 QKD_API qkd_status qkd_debug_set_option(qkd_workspace *ws, const char *name, const char *value);

@@ -13,6 +13,7 @@ src/array_and_matrix_operations.hpp) with batched, device-resident arrays:
   QKD_LDPC_irregular/_regular                     qkd_ldpc(H, alice, bob, qber, ...)
   its decode step alone, Bob's side of a link      reconcile(H, bob, syndrome, qber, ...)
   (no counterpart) key verification tags            verify_tags(H, bits, ...), reconcile(..., alice_tags=)
+  (no counterpart) privacy amplification            privacy_amplify(keys, out_bits, ..., keep=verified)
   generate_random_bit_array + introduce_errors    keygen(H, seeds, q_nominal, ...)
   run_trial over a batch + the batch reduction    run_trials(H, seeds, q_nominal, ...)
   seeds of QKD_LDPC_batch_simulation              make_seeds(simulation_seed, count)
@@ -44,6 +45,7 @@ __all__ = [
     "qber_range", "Workspace", "counters_to_stats", "decoder_flags", "trace_decode", "set_debug_option",
     "spec_replays", "check_lanes", "interactive_simulation", "reconcile", "ReconcileResult",
     "verify_key_words", "verify_expand_key", "verify_tags",
+    "privacy_key_words", "privacy_expand_key", "privacy_amplify",
 ]
 
 
@@ -446,6 +448,63 @@ def verify_tags(H: HMatrix, bits, hash_seed: int = 0, hash_words=None, tag_bits:
     N.check(N.lib().qkd_verify_tags_batch(H.handle, _ptr(bits), f, seed, _ptr(words), tag_bits, _ptr(tags),
                                           _stream(stream, H.device)))
     return tags
+
+
+class _Device:
+    """What _need_cuda asks of an HMatrix, for entries that take a device and no code."""
+
+    def __init__(self, index: int):
+        self.device = index
+
+
+def privacy_key_words(n_in: int, out_bits: int) -> int:
+    """Wp = ceil((n_in + out_bits - 1) / 64): the 64-bit words of the privacy amplification
+    hash's key string (qkd_privacy_key_words); 0 unless 1 <= out_bits <= n_in <= 2^20."""
+    if not (0 <= n_in < 2**32 and 0 <= out_bits < 2**32):
+        return 0
+    return int(N.lib().qkd_privacy_key_words(n_in, out_bits))
+
+
+def privacy_expand_key(hash_seed: int, n_in: int, out_bits: int) -> np.ndarray:
+    """The Wp words the seeded form of the hash uses (qkd_privacy_expand_key), as a numpy
+    uint64 array: to inspect, or to upload as hash_words."""
+    w = privacy_key_words(n_in, out_bits)
+    if w == 0:
+        raise QkdError(N.ERR_INVALID_ARG, "need 1 <= out_bits <= n_in <= 2^20")
+    out = np.zeros(w, np.uint64)
+    N.check(N.lib().qkd_privacy_expand_key(hash_seed & (2**64 - 1), n_in, out_bits, out.ctypes.data))
+    return out
+
+
+def privacy_amplify(keys, out_bits: int, hash_seed: int = 0, hash_words=None, keep=None, stream=None):
+    """Privacy amplification (qkd_privacy_amplify_batch): keys [F, n_in] uint8 on the GPU
+    (a key bit is byte & 1) hashed to out_bits bits each with the Hankel matrix of the key
+    string, out_i = XOR_p r[p + i] x_p; returns [F, ceil(out_bits / 64)] int64 bit
+    patterns, bit i of a frame in word i >> 6 at i & 63. The key string is hash_words
+    (privacy_key_words(n_in, out_bits) 64-bit words on the device, truly random: the
+    universal form) or, without them, expanded from hash_seed (a computational stand-in).
+    It must be independent of the verification hash's string. keep ([F] uint8, typically
+    ReconcileResult.verified): frames with 0 get all-zero words. To hash B corrected
+    frames as one block, pass bits.view(F // B, B * N)."""
+    _need_cuda(keys, torch.uint8, "keys")
+    if keys.dim() != 2 or keys.shape[0] < 1 or keys.shape[1] < 1:
+        raise QkdError(N.ERR_INVALID_ARG, f"keys must have shape [F, n_in], got {list(keys.shape)}")
+    f, n_in = int(keys.shape[0]), int(keys.shape[1])
+    if not isinstance(out_bits, int) or not 1 <= out_bits <= n_in:
+        raise QkdError(N.ERR_INVALID_ARG, f"out_bits must be in 1..{n_in}")
+    wp = privacy_key_words(n_in, out_bits)
+    if wp == 0:
+        raise QkdError(N.ERR_INVALID_ARG, "n_in exceeds 2^20 bits")
+    dev = _Device(keys.device.index)
+    if hash_words is not None:
+        _need_tags(hash_words, wp, "hash_words", dev)
+    if keep is not None:
+        _need_vec(keep, torch.uint8, f, "keep", dev)
+    seed = (0 if hash_seed is None else int(hash_seed)) & (2**64 - 1)
+    out = torch.empty(f, (out_bits + 63) // 64, dtype=torch.int64, device=keys.device)
+    N.check(N.lib().qkd_privacy_amplify_batch(dev.device, _ptr(keys), f, n_in, out_bits, seed, _ptr(hash_words),
+                                              _ptr(keep), _ptr(out), _stream(stream, dev.device)))
+    return out
 
 
 def keygen(H: HMatrix, seeds, q_nominal: float, seed_offset: int = 0, workspace=None,

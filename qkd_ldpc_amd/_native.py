@@ -67,6 +67,7 @@ EXPORTS = [
     "qkd_counters_merge", "qkd_debug_set_option", "qkd_debug_check_lanes",
     "qkd_reconcile_batch",
     "qkd_verify_key_words", "qkd_verify_expand_key", "qkd_verify_tags_batch", "qkd_reconcile_verify_batch",
+    "qkd_privacy_key_words", "qkd_privacy_expand_key", "qkd_privacy_amplify_batch",
 ]
 
 
@@ -129,6 +130,9 @@ def lib():
             "qkd_verify_key_words": (SZ, [I32]),
             "qkd_verify_expand_key": (st, [U64, I32, P]),
             "qkd_verify_tags_batch": (st, [P, P, SZ, U64, P, U32, P, P]),
+            "qkd_privacy_key_words": (SZ, [U32, U32]),
+            "qkd_privacy_expand_key": (st, [U64, U32, U32, P]),
+            "qkd_privacy_amplify_batch": (st, [C.c_int, P, SZ, U32, U32, U64, P, P, P, P]),
             "qkd_keygen_batch": (st, [P, P, P, U64, SZ, D, P, P, P, P]),
             "qkd_trials_batch": (st, [P, P, P, U64, SZ, D, U32, D, U32, P, P, P, P, P, P]),
             "qkd_counters_batch": (st, [P, P, P, SZ, P, C.c_int, P]),

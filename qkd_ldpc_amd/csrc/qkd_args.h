@@ -1,10 +1,13 @@
 // qkd_args.h — host-only argument checks of the batched entry points, free of
 // HIP so that a stand-alone host program can exercise them
-// (tests/native/reconcile_args_check.cpp, tests/native/verify_hash_check.cpp).
+// (tests/native/reconcile_args_check.cpp, tests/native/verify_hash_check.cpp,
+// tests/native/privacy_hash_check.cpp).
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include "qkd_privacy.h"
 
 namespace qkda {
 
@@ -43,6 +46,18 @@ inline const char* reconcile_verify_args_error(uint32_t tag_bits, const uint64_t
     if (!alice_tags && !tags_out) return "neither alice_tags nor tags_out given";
     if (alice_tags && !verified) return "alice_tags given without verified";
     if (!alice_tags && verified) return "verified given without alice_tags";
+    return nullptr;
+}
+
+// qkd_privacy_amplify_batch's arguments, the same way. hash_words and keep may
+// be NULL and are not looked at.
+inline const char* privacy_amplify_args_error(const uint8_t* keys, size_t n_frames, uint32_t n_in, uint32_t out_bits,
+                                              const uint64_t* out_words) {
+    if (!keys || !out_words) return "null argument";
+    if (n_frames == 0) return "n_frames must be > 0";
+    if (n_frames > 0xffffffffull) return "n_frames too large";
+    if (n_in < 1 || n_in > qkdv::kPrivacyMaxBits) return "n_in must be in 1..QKD_PRIVACY_MAX_BITS";
+    if (out_bits < 1 || out_bits > n_in) return "out_bits must be in 1..n_in";
     return nullptr;
 }
 
