@@ -62,6 +62,22 @@ typedef enum qkd_status {
 #define QKD_FLAG_THRESHOLD 0x1u  /* CFG.ENABLE_SUM_PRODUCT_MSG_LLR_THRESHOLD
                                     (qkd_ldpc_algorithm.cpp:246,313)         */
 
+/* The binary64 check rule extended to zero LLRs (QKD_VARIANT_SP_F64 only; taken
+ * by qkd_decode_batch, implied by qkd_reconcile_adaptive_batch). The
+ * reference's rule, c2b_k = 2 atanh(P / t_k) with P = sigma t_0 t_1 ... over
+ * the published t_k = tanh(b2c_k / 2) of a check, is 0 / 0 when a t_k is zero
+ * (qkd_ldpc_algorithm.cpp:231-241), and a punctured bit IS a zero LLR. With z
+ * the number of t_k equal to zero (either sign) and sigma = -1 if the check's
+ * syndrome bit is set, else +1:
+ *   z = 0   the reference rule, unchanged;
+ *   z = 1   the edge whose t is zero gets 2 atanh(P'), P' = sigma times the
+ *           non-zero t in ascending edge order; every other edge gets +0.0;
+ *   z >= 2  every edge gets +0.0.
+ * Clamp, bit phase, decision, stopping rule, iteration count and flags are the
+ * reference's; a frame in which no t is ever zero decodes bit for bit as
+ * without the flag. Launches with the flag run exact iterations only. */
+#define QKD_FLAG_ERASURES 0x2u
+
 /* Check-node rule (flag bits 4-5). QKD_VARIANT_SP_F64 is the reference's
  * decoder (qkd_ldpc_algorithm.cpp:175-345), bit-exact. The other two are
  * build-defined variants with binary32 messages and totals (SURVEY.md §8(d),
@@ -92,6 +108,7 @@ typedef enum qkd_status {
 
 typedef struct qkd_code qkd_code;
 typedef struct qkd_workspace qkd_workspace;
+typedef struct qkd_adapt qkd_adapt;
 
 typedef struct qkd_code_info {
     int32_t n_bits;              /* H_matrix::num_bit_nodes                  */
@@ -169,7 +186,9 @@ QKD_API qkd_status qkd_syndrome_batch(const qkd_code *code, const uint8_t *bits,
  * hard decision), iterations[F] (SP_result::iterations_num) and
  * syndromes_match[F] (SP_result::syndromes_match). msg_threshold is
  * CFG.SUM_PRODUCT_MSG_LLR_THRESHOLD, applied when QKD_FLAG_THRESHOLD is set.
- * bits_out may be NULL. */
+ * bits_out may be NULL. The only entry that takes QKD_FLAG_ERASURES (LLRs that
+ * may be zero; QKD_VARIANT_SP_F64 only, QKD_ERR_INVALID_ARG with another
+ * variant before any device work). */
 QKD_API qkd_status qkd_decode_batch(const qkd_code *code, qkd_workspace *ws, const double *llr,
                             const uint8_t *syndrome, size_t n_frames, uint32_t max_iterations,
                             double msg_threshold, uint32_t flags, uint8_t *bits_out,
@@ -266,6 +285,85 @@ QKD_API qkd_status qkd_reconcile_verify_batch(const qkd_code *code, qkd_workspac
                                uint32_t *corrected, uint64_t hash_seed, const uint64_t *hash_words,
                                uint32_t tag_bits, const uint64_t *alice_tags, uint64_t *tags_out,
                                uint8_t *verified, void *stream);
+
+/* ---- rate adaptation: punctured and shortened frames -------------------------
+ * One mother code serves a range of channels (Elkouss et al.): of the N bits of
+ * a frame, p punctured positions hold Alice's private random bits, which are
+ * never disclosed (Bob's LLR there is 0: the rate goes up), s shortened
+ * positions hold 0 on both sides (Bob's LLR there is +known_llr: the rate goes
+ * down), and the other n_payload = N - p - s positions hold the key: payload
+ * bit k lives at the k-th position, in ascending order, that is neither
+ * punctured nor shortened. A qkd_adapt is such a choice for one code, uploaded
+ * once; immutable and shareable like a code. It must be destroyed before its
+ * code. No reference counterpart (the reference has one rate per matrix). */
+typedef struct qkd_adapt_info {
+    int32_t n_bits;
+    int32_t n_payload;           /* N - p - s                                */
+    int32_t n_punctured;
+    int32_t n_shortened;
+} qkd_adapt_info;
+
+/* punctured[p], shortened[s]: host arrays of positions (NULL with a count of
+ * 0). QKD_ERR_INVALID_ARG unless every position is in [0, N), all p + s are
+ * distinct and n_payload >= 1. */
+QKD_API qkd_adapt *qkd_adapt_create(const qkd_code *code, const int32_t *punctured, int32_t p,
+                                    const int32_t *shortened, int32_t s, qkd_status *status);
+QKD_API void qkd_adapt_destroy(qkd_adapt *adapt);
+QKD_API qkd_status qkd_adapt_get_info(const qkd_adapt *adapt, qkd_adapt_info *info);
+
+/* A deterministic "untainted" choice of `count` positions of a code given as a
+ * check-side CSR (as qkd_code_create), which both sides compute from a shared
+ * seed. Host only, no device. Candidates are visited in the order of a
+ * Fisher-Yates shuffle of 0..N-1 driven by the library's SplitMix64 counter
+ * form: R[k] = mix(seed + (k + 1) * 0x9E3779B97F4A7C15) (qkd_verify_expand_key),
+ * j = R[k] mod (i + 1), swap entries i and j, for i from N-1 down to 1, k
+ * counting up from 0. Pass 1 takes a candidate when none of its checks is
+ * adjacent to an earlier pick and stops at `count`; pass 2 fills any remainder
+ * with the untaken candidates in the same order. positions_host[count]: the
+ * positions in the order they were taken; *untainted_out (may be NULL): how
+ * many pass 1 took. A caller punctures the first p and shortens the next s.
+ * 0 <= count <= N. */
+QKD_API qkd_status qkd_adapt_positions(int32_t n_bits, int32_t n_checks, const int32_t *check_ptr,
+                                       const int32_t *check_idx, int32_t count, uint64_t seed,
+                                       int32_t *positions_host, int32_t *untainted_out);
+
+/* Alice's half is qkd_adapt_embed_batch followed by qkd_syndrome_batch.
+ * payload[F * n_payload] 0/1 bytes (only byte & 1 counts; rows of any
+ * alignment), fill[F * p] her random bits for the punctured positions in the
+ * order of the plan's punctured list (required exactly when p > 0; there is
+ * deliberately no seeded form), shortened positions are written as 0 ->
+ * frames[F * N]. extract: frames[F * N] -> payload[F * n_payload] (byte & 1).
+ * All arrays on the plan's device. Kernel launches on the stream only: no
+ * workspace, no allocation, no host copy, no synchronisation; capturable. */
+QKD_API qkd_status qkd_adapt_embed_batch(const qkd_adapt *adapt, const uint8_t *payload, size_t n_frames,
+                                         const uint8_t *fill, uint8_t *frames, void *stream);
+QKD_API qkd_status qkd_adapt_extract_batch(const qkd_adapt *adapt, const uint8_t *frames, size_t n_frames,
+                                           uint8_t *payload, void *stream);
+
+/* Bob's half. For every frame the N-bit decision, iterations and
+ * syndromes_match equal what qkd_decode_batch returns with
+ * flags | QKD_FLAG_ERASURES for the LLRs
+ *   payload position holding Bob's bit b:  b ? -log_p : +log_p,
+ *                                          log_p = log((1 - q) / q) as qkd_reconcile_batch
+ *   punctured position:                    +0.0
+ *   shortened position:                    +known_llr
+ * but no LLR array exists: the decoder reads one class byte per bit, written by
+ * one small kernel from bob_payload[F * n_payload] and the plan.
+ * payload_out[F * n_payload] (required): the payload of the decision;
+ * frames_out[F * N] (may be NULL): the whole decision; corrected[F] (may be
+ * NULL): popcount(payload_out ^ bob_payload). known_llr must be finite and > 0
+ * (the clamp's value makes a shortened bit publish t = 1.0 exactly); the plan
+ * must have been created for `code`; everything else is validated as
+ * qkd_reconcile_batch does. QKD_FLAG_ERASURES is implied. Only
+ * QKD_VARIANT_SP_F64: another variant returns QKD_ERR_UNSUPPORTED. Code sizes as
+ * qkd_decode_batch. Exact iterations only (no folded first iteration, tables or
+ * speculation in this mode). */
+QKD_API qkd_status qkd_reconcile_adaptive_batch(const qkd_code *code, qkd_workspace *ws, const qkd_adapt *adapt,
+                                                const uint8_t *bob_payload, const uint8_t *syndrome,
+                                                size_t n_frames, double qber, double known_llr,
+                                                uint32_t max_iterations, double msg_threshold, uint32_t flags,
+                                                uint8_t *payload_out, uint8_t *frames_out, uint32_t *iterations,
+                                                uint8_t *syndromes_match, uint32_t *corrected, void *stream);
 
 /* ---- privacy amplification --------------------------------------------------
  * The last step before a secret key: the corrected (and verified) key is

@@ -14,6 +14,8 @@ src/array_and_matrix_operations.hpp) with batched, device-resident arrays:
   its decode step alone, Bob's side of a link      reconcile(H, bob, syndrome, qber, ...)
   (no counterpart) key verification tags            verify_tags(H, bits, ...), reconcile(..., alice_tags=)
   (no counterpart) privacy amplification            privacy_amplify(keys, out_bits, ..., keep=verified)
+  (no counterpart) punctured / shortened frames     AdaptPlan, adapt_embed, adapt_extract,
+                                                    reconcile_adaptive(H, plan, bob_payload, ...)
   generate_random_bit_array + introduce_errors    keygen(H, seeds, q_nominal, ...)
   run_trial over a batch + the batch reduction    run_trials(H, seeds, q_nominal, ...)
   seeds of QKD_LDPC_batch_simulation              make_seeds(simulation_seed, count)
@@ -46,19 +48,24 @@ __all__ = [
     "spec_replays", "check_lanes", "interactive_simulation", "reconcile", "ReconcileResult",
     "verify_key_words", "verify_expand_key", "verify_tags",
     "privacy_key_words", "privacy_expand_key", "privacy_amplify",
+    "AdaptPlan", "adapt_positions", "adapt_embed", "adapt_extract", "reconcile_adaptive",
 ]
 
 
 def decoder_flags(threshold_enabled: bool = True, variant: str = "sp_f64",
                   minsum_scale: float | None = None, minsum_offset: float | None = None,
-                  minsum_self_correct: bool = False) -> int:
+                  minsum_self_correct: bool = False, erasures: bool = False) -> int:
     """Flag word of the decode entry points: the reference's threshold switch
     (CFG.ENABLE_SUM_PRODUCT_MSG_LLR_THRESHOLD) and the check-node rule:
     "sp_f64" (the reference, bit-exact), "sp_f32" or "minsum" (build-defined
-    binary32 variants; minsum_scale in (0, 1), a multiple of 1/256)."""
+    binary32 variants; minsum_scale in (0, 1), a multiple of 1/256).
+    erasures: QKD_FLAG_ERASURES, the binary64 rule extended to zero LLRs
+    (sum_product_decoding only; the library rejects it with another variant)."""
     if variant not in N.VARIANTS:
         raise ValueError(f"unknown decoder variant {variant!r}; one of {sorted(N.VARIANTS)}")
     flags = (FLAG_THRESHOLD if threshold_enabled else 0) | N.VARIANTS[variant]
+    if erasures:
+        flags |= N.FLAG_ERASURES
     if minsum_scale is not None:
         if variant != "minsum":
             raise ValueError("minsum_scale applies to variant='minsum' only")
@@ -291,9 +298,11 @@ def sum_product_decoding(H: HMatrix, llr, syndrome, max_iterations: int = 50,
                          msg_threshold: float = 100.0, threshold_enabled: bool = True,
                          want_bits: bool = True, workspace=None, stream=None,
                          variant: str = "sp_f64", minsum_scale: float | None = None,
-                         minsum_offset: float | None = None, minsum_self_correct: bool = False) -> SPResult:
+                         minsum_offset: float | None = None, minsum_self_correct: bool = False,
+                         erasures: bool = False) -> SPResult:
     """sum_product_decoding_irregular/_regular (qkd_ldpc_algorithm.cpp:3-345), batched.
-    llr [F, N] float64, syndrome [F, M] uint8 (0/1)."""
+    llr [F, N] float64, syndrome [F, M] uint8 (0/1). erasures: the check rule defined
+    at zero LLRs (QKD_FLAG_ERASURES; variant "sp_f64" only), for punctured bits."""
     _need_cuda(llr, torch.float64, "llr", H)
     _need_cuda(syndrome, torch.uint8, "syndrome", H)
     f = _frames(llr, H.num_bit_nodes, "llr")
@@ -302,7 +311,8 @@ def sum_product_decoding(H: HMatrix, llr, syndrome, max_iterations: int = 50,
     bits = torch.empty((f, H.num_bit_nodes), dtype=torch.uint8, device=dev) if want_bits else None
     iters = torch.empty(f, dtype=torch.int32, device=dev)
     ok = torch.empty(f, dtype=torch.uint8, device=dev)
-    flags = decoder_flags(threshold_enabled, variant, minsum_scale, minsum_offset, minsum_self_correct)
+    flags = decoder_flags(threshold_enabled, variant, minsum_scale, minsum_offset, minsum_self_correct,
+                          erasures)
     N.check(N.lib().qkd_decode_batch(H.handle, _ws(workspace), _ptr(llr), _ptr(syndrome), f,
                                      max_iterations, msg_threshold, flags, _ptr(bits), _ptr(iters),
                                      _ptr(ok), _stream(stream, H.device)))
@@ -354,6 +364,8 @@ class ReconcileResult:
     # tags (int64 bit patterns) and syndromes_match & (tag == Alice's tag)
     tags: "torch.Tensor | None" = None
     verified: "torch.Tensor | None" = None
+    # reconcile_adaptive with want_frames: the whole N-bit decisions (bits is the payload)
+    frames: "torch.Tensor | None" = None
 
 
 def reconcile(H: HMatrix, bob, syndrome, qber: float, max_iterations: int = 50,
@@ -448,6 +460,140 @@ def verify_tags(H: HMatrix, bits, hash_seed: int = 0, hash_words=None, tag_bits:
     N.check(N.lib().qkd_verify_tags_batch(H.handle, _ptr(bits), f, seed, _ptr(words), tag_bits, _ptr(tags),
                                           _stream(stream, H.device)))
     return tags
+
+
+def _csr(H):
+    """(n, m, check_ptr, check_idx) of an HMatrix, or of a (n_bits, check_ptr, check_idx)
+    tuple: the host helpers need no device."""
+    if isinstance(H, HMatrix):
+        cp, ci, _, _ = H.adjacency()
+        return H.num_bit_nodes, H.num_check_nodes, cp, ci
+    n, cp, ci = H
+    cp = np.ascontiguousarray(cp, dtype=np.int32)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    return int(n), cp.size - 1, cp, ci
+
+
+def adapt_positions(H, count: int, seed: int):
+    """qkd_adapt_positions: a deterministic "untainted" choice of `count` positions that
+    Alice and Bob both compute from a shared seed (a seeded Fisher-Yates order; first the
+    candidates none of whose checks touches an earlier pick, then the rest). H: an HMatrix,
+    or (n_bits, check_ptr, check_idx) on a machine without a device. Returns (positions
+    int32 numpy array in the order taken, untainted count)."""
+    n, m, cp, ci = _csr(H)
+    out = np.zeros(max(int(count), 1), np.int32)
+    unt = C.c_int32(0)
+    N.check(N.lib().qkd_adapt_positions(n, m, cp.ctypes.data, ci.ctypes.data, int(count),
+                                        int(seed) & (2**64 - 1), out.ctypes.data, C.byref(unt)))
+    return out[:int(count)], int(unt.value)
+
+
+class AdaptPlan:
+    """A rate-adaptation plan of one code (qkd_adapt): `punctured` positions hold Alice's
+    private random bits (Bob's LLR 0), `shortened` positions hold 0 on both sides (Bob's
+    LLR +known_llr); payload bit k lives at the k-th other position, ascending. Uploaded
+    once, immutable; close it before its HMatrix."""
+
+    def __init__(self, H: HMatrix, punctured=(), shortened=()):
+        pu = np.ascontiguousarray(punctured, dtype=np.int32).reshape(-1)
+        sh = np.ascontiguousarray(shortened, dtype=np.int32).reshape(-1)
+        st = C.c_int(0)
+        h = N.lib().qkd_adapt_create(H.handle, pu.ctypes.data if pu.size else None, pu.size,
+                                     sh.ctypes.data if sh.size else None, sh.size, C.byref(st))
+        if not h:
+            raise QkdError(st.value, N.last_error())
+        self._h = C.c_void_p(h)
+        self._H = H            # (the plan points into its code)
+        info = N.AdaptInfo()
+        N.check(N.lib().qkd_adapt_get_info(self._h, C.byref(info)))
+        self.n_bits = info.n_bits
+        self.n_payload = info.n_payload
+        self.n_punctured = info.n_punctured
+        self.n_shortened = info.n_shortened
+        self.device = H.device
+        self.punctured = pu.copy()
+        self.shortened = sh.copy()
+
+    @classmethod
+    def choose(cls, H: HMatrix, count: int, p: int, seed: int) -> "AdaptPlan":
+        """`count` positions from adapt_positions(H, count, seed): the first p punctured,
+        the other count - p shortened."""
+        if not 0 <= p <= count:
+            raise QkdError(N.ERR_INVALID_ARG, f"p must be in 0..{count}")
+        pos, _ = adapt_positions(H, count, seed)
+        return cls(H, pos[:p], pos[p:])
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            N.lib().qkd_adapt_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def adapt_embed(plan: AdaptPlan, payload, fill=None, stream=None):
+    """qkd_adapt_embed_batch: payload [F, n_payload] uint8 (a bit is byte & 1) and, exactly
+    when the plan punctures, fill [F, p] uint8 (Alice's private random bits, in the order
+    of the plan's punctured list) -> frames [F, N] uint8; shortened positions are 0.
+    Alice's half of the protocol is this followed by calculate_syndrome."""
+    _need_cuda(payload, torch.uint8, "payload", plan)
+    f = _frames(payload, plan.n_payload, "payload")
+    if fill is not None:
+        _need_cuda(fill, torch.uint8, "fill", plan)
+        if plan.n_punctured == 0:
+            raise QkdError(N.ERR_INVALID_ARG, "fill given for a plan without punctured positions")
+        _frames(fill, plan.n_punctured, "fill", f)
+    frames = torch.empty((f, plan.n_bits), dtype=torch.uint8, device=payload.device)
+    N.check(N.lib().qkd_adapt_embed_batch(plan.handle, _ptr(payload), f, _ptr(fill), _ptr(frames),
+                                          _stream(stream, plan.device)))
+    return frames
+
+
+def adapt_extract(plan: AdaptPlan, frames, stream=None):
+    """qkd_adapt_extract_batch: frames [F, N] uint8 -> their payload [F, n_payload] (byte & 1)."""
+    _need_cuda(frames, torch.uint8, "frames", plan)
+    f = _frames(frames, plan.n_bits, "frames")
+    out = torch.empty((f, plan.n_payload), dtype=torch.uint8, device=frames.device)
+    N.check(N.lib().qkd_adapt_extract_batch(plan.handle, _ptr(frames), f, _ptr(out),
+                                            _stream(stream, plan.device)))
+    return out
+
+
+def reconcile_adaptive(H: HMatrix, plan: AdaptPlan, bob_payload, syndrome, qber: float,
+                       known_llr: float = 100.0, max_iterations: int = 50, msg_threshold: float = 100.0,
+                       threshold_enabled: bool = True, want_corrected: bool = True,
+                       want_frames: bool = False, workspace=None, stream=None) -> ReconcileResult:
+    """Bob's side with punctured and shortened frames (qkd_reconcile_adaptive_batch):
+    bob_payload [F, n_payload] uint8, syndrome [F, M] uint8 of Alice's embedded frames. The
+    decision equals sum_product_decoding(erasures=True) on the LLRs +-log((1-q)/q) at the
+    payload positions, +0.0 at the punctured and +known_llr at the shortened ones, without
+    that array ever existing. bits: the payload of the decision; corrected:
+    popcount(bits ^ bob_payload); frames (want_frames): the whole N-bit decisions. The
+    default known_llr is the default clamp, so a shortened bit publishes t = 1.0 exactly."""
+    _need_cuda(bob_payload, torch.uint8, "bob_payload", H)
+    _need_cuda(syndrome, torch.uint8, "syndrome", H)
+    f = _frames(bob_payload, plan.n_payload, "bob_payload")
+    _frames(syndrome, H.num_check_nodes, "syndrome", f)
+    dev = bob_payload.device
+    bits = torch.empty((f, plan.n_payload), dtype=torch.uint8, device=dev)
+    frames = torch.empty((f, H.num_bit_nodes), dtype=torch.uint8, device=dev) if want_frames else None
+    iters = torch.empty(f, dtype=torch.int32, device=dev)
+    ok = torch.empty(f, dtype=torch.uint8, device=dev)
+    corrected = torch.empty(f, dtype=torch.int32, device=dev) if want_corrected else None
+    flags = decoder_flags(threshold_enabled, "sp_f64")
+    N.check(N.lib().qkd_reconcile_adaptive_batch(
+        H.handle, _ws(workspace), plan.handle, _ptr(bob_payload), _ptr(syndrome), f, qber, known_llr,
+        max_iterations, msg_threshold, flags, _ptr(bits), _ptr(frames), _ptr(iters), _ptr(ok), _ptr(corrected),
+        _stream(stream, H.device)))
+    return ReconcileResult(iters, ok, bits, corrected, frames=frames)
 
 
 class _Device:

@@ -46,6 +46,7 @@ ERR_IO = 7
 ERR_UNSUPPORTED = 8
 
 FLAG_THRESHOLD = 0x1
+FLAG_ERASURES = 0x2    # QKD_FLAG_ERASURES: the binary64 rule extended to zero LLRs
 READ_SORT_ROWS = 0x1   # qkd_code_from_alist_ex
 # decoder variants (include/qkd_ldpc.h: QKD_VARIANT_*)
 VARIANTS = {"sp_f64": 0x00, "sp_f32": 0x10, "minsum": 0x20}
@@ -68,12 +69,18 @@ EXPORTS = [
     "qkd_reconcile_batch",
     "qkd_verify_key_words", "qkd_verify_expand_key", "qkd_verify_tags_batch", "qkd_reconcile_verify_batch",
     "qkd_privacy_key_words", "qkd_privacy_expand_key", "qkd_privacy_amplify_batch",
+    "qkd_adapt_create", "qkd_adapt_destroy", "qkd_adapt_get_info", "qkd_adapt_positions",
+    "qkd_adapt_embed_batch", "qkd_adapt_extract_batch", "qkd_reconcile_adaptive_batch",
 ]
 
 
 class CodeInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_bits", "n_checks", "n_edges", "max_bit_degree",
                                          "max_check_degree", "is_regular", "device")]
+
+
+class AdaptInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_bits", "n_payload", "n_punctured", "n_shortened")]
 
 
 class Counters(C.Structure):
@@ -133,6 +140,13 @@ def lib():
             "qkd_privacy_key_words": (SZ, [U32, U32]),
             "qkd_privacy_expand_key": (st, [U64, U32, U32, P]),
             "qkd_privacy_amplify_batch": (st, [C.c_int, P, SZ, U32, U32, U64, P, P, P, P]),
+            "qkd_adapt_create": (P, [P, P, I32, P, I32, C.POINTER(st)]),
+            "qkd_adapt_destroy": (None, [P]),
+            "qkd_adapt_get_info": (st, [P, C.POINTER(AdaptInfo)]),
+            "qkd_adapt_positions": (st, [I32, I32, P, P, I32, U64, P, C.POINTER(I32)]),
+            "qkd_adapt_embed_batch": (st, [P, P, SZ, P, P, P]),
+            "qkd_adapt_extract_batch": (st, [P, P, SZ, P, P]),
+            "qkd_reconcile_adaptive_batch": (st, [P, P, P, P, P, SZ, D, D, U32, D, U32, P, P, P, P, P, P]),
             "qkd_keygen_batch": (st, [P, P, P, U64, SZ, D, P, P, P, P]),
             "qkd_trials_batch": (st, [P, P, P, U64, SZ, D, U32, D, U32, P, P, P, P, P, P]),
             "qkd_counters_batch": (st, [P, P, P, SZ, P, C.c_int, P]),

@@ -1,0 +1,212 @@
+// adapt.hip — rate adaptation of one mother code by puncturing and shortening
+// (Elkouss et al.): the plan object (qkd_adapt), the kernels that place a
+// payload in a frame and take it out again, and the class bytes the decoder of
+// qkd_reconcile_adaptive_batch reads instead of per-bit LLRs.
+//
+// A frame of N bits holds n_payload = N - p - s key bits (payload bit k at the
+// k-th position, ascending, that is neither punctured nor shortened), p
+// punctured bits (Alice's private random bits, never sent: Bob's LLR is 0) and
+// s shortened bits (0 on both sides: Bob's LLR is +known).
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "qkd_decode.h"
+#include "qkd_internal.h"
+
+namespace qkd {
+
+constexpr int kAdaptBlock = 256;
+
+// cls[f * n + i] from the map src (in whichever bit order the decoder reads)
+__global__ __launch_bounds__(kAdaptBlock) void adapt_class_kernel(const int32_t* __restrict__ src,
+                                                                  const uint8_t* __restrict__ payload, uint32_t n,
+                                                                  uint32_t n_payload, uint8_t* __restrict__ cls) {
+    const uint32_t i = blockIdx.x * kAdaptBlock + threadIdx.x;
+    const size_t f = blockIdx.y;
+    if (i >= n) return;
+    const int32_t k = src[i];
+    uint8_t v;
+    if (k >= 0) v = payload[f * n_payload + (uint32_t)k] & 1u;
+    else v = k == kSrcPunctured ? 2u : 3u;
+    cls[f * n + i] = v;
+}
+
+// frames[f * n + i] from the embedding map (qkd_adapt::d_emb)
+__global__ __launch_bounds__(kAdaptBlock) void adapt_embed_kernel(const int32_t* __restrict__ emb,
+                                                                  const uint8_t* __restrict__ payload,
+                                                                  const uint8_t* __restrict__ fill, uint32_t n,
+                                                                  uint32_t n_payload, uint32_t p,
+                                                                  uint8_t* __restrict__ frames) {
+    const uint32_t i = blockIdx.x * kAdaptBlock + threadIdx.x;
+    const size_t f = blockIdx.y;
+    if (i >= n) return;
+    const int32_t k = emb[i];
+    uint8_t v = 0;                                      // a shortened bit
+    if (k >= 0) v = payload[f * n_payload + (uint32_t)k] & 1u;
+    else if (k <= -2) v = fill[f * p + (uint32_t)(-2 - k)] & 1u;
+    frames[f * n + i] = v;
+}
+
+// payload[f * n_payload + src[i]] = frames[f * n + i] & 1 for the payload bits
+__global__ __launch_bounds__(kAdaptBlock) void adapt_extract_kernel(const int32_t* __restrict__ src,
+                                                                    const uint8_t* __restrict__ frames, uint32_t n,
+                                                                    uint32_t n_payload, uint8_t* __restrict__ payload) {
+    const uint32_t i = blockIdx.x * kAdaptBlock + threadIdx.x;
+    const size_t f = blockIdx.y;
+    if (i >= n) return;
+    const int32_t k = src[i];
+    if (k >= 0) payload[f * n_payload + (uint32_t)k] = frames[f * n + i] & 1u;
+}
+
+// (grid y: at most 65535 frames per launch)
+constexpr size_t kAdaptFramesPerLaunch = 65535;
+
+hipError_t launch_adapt_classes(const int32_t* src, const uint8_t* payload, uint32_t n, uint32_t n_payload,
+                                uint32_t n_frames, uint8_t* cls, hipStream_t stream) {
+    for (size_t f0 = 0; f0 < n_frames; f0 += kAdaptFramesPerLaunch) {
+        const size_t nf = std::min(kAdaptFramesPerLaunch, (size_t)n_frames - f0);
+        hipLaunchKernelGGL(adapt_class_kernel, dim3((n + kAdaptBlock - 1) / kAdaptBlock, (unsigned)nf),
+                           dim3(kAdaptBlock), 0, stream, src, payload + f0 * n_payload, n, n_payload, cls + f0 * n);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+static void adapt_free(qkd_adapt* a) {
+    DeviceGuard g(a->device);
+    if (a->d_src_orig) (void)hipFree(a->d_src_orig);
+    if (a->d_src_int) (void)hipFree(a->d_src_int);
+    if (a->d_emb) (void)hipFree(a->d_emb);
+    delete a;
+}
+
+static qkd_status adapt_build(qkd_adapt* a, const qkd_code* c, const int32_t* punctured, int32_t p,
+                              const int32_t* shortened, int32_t s) {
+    const int32_t n = c->n;
+    if (p < 0 || s < 0 || (p > 0 && !punctured) || (s > 0 && !shortened))
+        return set_error(QKD_ERR_INVALID_ARG, "qkd_adapt_create: bad position lists");
+    if ((int64_t)p + s >= n) return set_error(QKD_ERR_INVALID_ARG, "qkd_adapt_create: no payload bit left (p + s >= N)");
+    // emb as in qkd_adapt; every position starts as payload
+    std::vector<int32_t> emb(n, 0);
+    for (int32_t r = 0; r < p + s; ++r) {
+        const int32_t pos = r < p ? punctured[r] : shortened[r - p];
+        if (pos < 0 || pos >= n)
+            return set_error(QKD_ERR_INVALID_ARG, "qkd_adapt_create: position %d out of range [0,%d)", pos, n);
+        if (emb[pos] != 0) return set_error(QKD_ERR_INVALID_ARG, "qkd_adapt_create: position %d given twice", pos);
+        emb[pos] = r < p ? -2 - r : -1;
+    }
+    std::vector<int32_t> src(n), src_int(n), perm(n);
+    int32_t k = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        if (emb[i] == 0) emb[i] = k++;
+        src[i] = emb[i] >= 0 ? emb[i] : (emb[i] == -1 ? kSrcShortened : kSrcPunctured);
+    }
+    a->code = c;
+    a->device = c->device;
+    a->n = n;
+    a->n_payload = n - p - s;
+    a->p = p;
+    a->s = s;
+    DeviceGuard g(c->device);
+    QKD_HIP(hipMemcpy(perm.data(), c->d_perm, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int32_t q = 0; q < n; ++q) {
+        if (perm[q] < 0 || perm[q] >= n) return set_error(QKD_ERR_BAD_CODE, "qkd_adapt_create: bad bit order");
+        src_int[q] = src[perm[q]];
+    }
+    const size_t bytes = (size_t)n * sizeof(int32_t);
+    QKD_HIP(hipMalloc(&a->d_src_orig, bytes));
+    QKD_HIP(hipMalloc(&a->d_src_int, bytes));
+    QKD_HIP(hipMalloc(&a->d_emb, bytes));
+    QKD_HIP(hipMemcpy(a->d_src_orig, src.data(), bytes, hipMemcpyHostToDevice));
+    QKD_HIP(hipMemcpy(a->d_src_int, src_int.data(), bytes, hipMemcpyHostToDevice));
+    QKD_HIP(hipMemcpy(a->d_emb, emb.data(), bytes, hipMemcpyHostToDevice));
+    return QKD_OK;
+}
+
+static qkd_status adapt_frames_check(const qkd_adapt* a, const void* in, const void* out, size_t n_frames) {
+    if (!a || !in || !out) return set_error(QKD_ERR_INVALID_ARG, "null argument");
+    if (n_frames == 0) return set_error(QKD_ERR_INVALID_ARG, "n_frames must be > 0");
+    if (n_frames > 0xffffffffull) return set_error(QKD_ERR_INVALID_ARG, "n_frames too large");
+    return QKD_OK;
+}
+
+}  // namespace qkd
+
+using namespace qkd;
+
+extern "C" {
+
+qkd_adapt* qkd_adapt_create(const qkd_code* code, const int32_t* punctured, int32_t p, const int32_t* shortened,
+                            int32_t s, qkd_status* status) {
+    clear_error();
+    qkd_status st = QKD_OK;
+    qkd_adapt* a = nullptr;
+    if (!code) {
+        st = set_error(QKD_ERR_INVALID_ARG, "null code");
+    } else if (!(a = new (std::nothrow) qkd_adapt())) {
+        st = set_error(QKD_ERR_OUT_OF_MEMORY, "out of host memory");
+    } else {
+        a->device = code->device;
+        st = adapt_build(a, code, punctured, p, shortened, s);
+        if (st != QKD_OK) {
+            adapt_free(a);
+            a = nullptr;
+        }
+    }
+    if (status) *status = st;
+    return a;
+}
+
+void qkd_adapt_destroy(qkd_adapt* a) {
+    if (a) adapt_free(a);
+}
+
+qkd_status qkd_adapt_get_info(const qkd_adapt* a, qkd_adapt_info* info) {
+    if (!a || !info) return set_error(QKD_ERR_INVALID_ARG, "null argument");
+    info->n_bits = a->n;
+    info->n_payload = a->n_payload;
+    info->n_punctured = a->p;
+    info->n_shortened = a->s;
+    return QKD_OK;
+}
+
+qkd_status qkd_adapt_embed_batch(const qkd_adapt* a, const uint8_t* payload, size_t n_frames, const uint8_t* fill,
+                                 uint8_t* frames, void* stream) {
+    clear_error();
+    qkd_status s = adapt_frames_check(a, payload, frames, n_frames);
+    if (s != QKD_OK) return s;
+    if ((a->p > 0) != (fill != nullptr))
+        return set_error(QKD_ERR_INVALID_ARG, "fill is required exactly when the plan punctures");
+    DeviceGuard g(a->device);
+    const uint32_t n = (uint32_t)a->n;
+    for (size_t f0 = 0; f0 < n_frames; f0 += kAdaptFramesPerLaunch) {
+        const size_t nf = std::min(kAdaptFramesPerLaunch, n_frames - f0);
+        hipLaunchKernelGGL(adapt_embed_kernel, dim3((n + kAdaptBlock - 1) / kAdaptBlock, (unsigned)nf),
+                           dim3(kAdaptBlock), 0, (hipStream_t)stream, a->d_emb, payload + f0 * (size_t)a->n_payload,
+                           fill ? fill + f0 * (size_t)a->p : nullptr, n, (uint32_t)a->n_payload, (uint32_t)a->p,
+                           frames + f0 * n);
+        QKD_HIP(hipGetLastError());
+    }
+    return QKD_OK;
+}
+
+qkd_status qkd_adapt_extract_batch(const qkd_adapt* a, const uint8_t* frames, size_t n_frames, uint8_t* payload,
+                                   void* stream) {
+    clear_error();
+    qkd_status s = adapt_frames_check(a, frames, payload, n_frames);
+    if (s != QKD_OK) return s;
+    DeviceGuard g(a->device);
+    const uint32_t n = (uint32_t)a->n;
+    for (size_t f0 = 0; f0 < n_frames; f0 += kAdaptFramesPerLaunch) {
+        const size_t nf = std::min(kAdaptFramesPerLaunch, n_frames - f0);
+        hipLaunchKernelGGL(adapt_extract_kernel, dim3((n + kAdaptBlock - 1) / kAdaptBlock, (unsigned)nf),
+                           dim3(kAdaptBlock), 0, (hipStream_t)stream, a->d_src_orig, frames + f0 * n, n,
+                           (uint32_t)a->n_payload, payload + f0 * (size_t)a->n_payload);
+        QKD_HIP(hipGetLastError());
+    }
+    return QKD_OK;
+}
+
+}  // extern "C"

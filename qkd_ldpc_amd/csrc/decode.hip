@@ -63,7 +63,7 @@ namespace qkd {
 // gathers/scatters coalesced saves 24 %: the phase is bound by the two
 // together, not by fp64 latency (working on two tasks at once, to interleave
 // two dependency chains, measured no gain).
-template <int SRC, bool CLAMP, int DC, int RULE, typename T>
+template <int SRC, bool CLAMP, int DC, int RULE, bool ERA = false, typename T>
 __device__ __forceinline__ void check_phase(const uint2* __restrict__ plan, const uint32_t* tsyn,
                                             const T* total, const uint16_t* t2idx, const double* tab2,
                                             T* __restrict__ c2b, T* row, int n_tasks, int n_pad, T thr,
@@ -88,7 +88,7 @@ __device__ __forceinline__ void check_phase(const uint2* __restrict__ plan, cons
         const T a = edge_in<SRC, CLAMP, RULE>(x, o, thr);
         row[lane] = a;
         wave_lds_sync();
-        return edge_out<CLAMP, DC, RULE>(a, w, sbit(w), lane, thr, row, ms_scale, ms_offset);
+        return edge_out<CLAMP, DC, RULE, ERA>(a, w, sbit(w), lane, thr, row, ms_scale, ms_offset);
     };
     uint2 wa = pl[t * 64];
     uint2 wb = pl[(t + NW) * 64];
@@ -286,9 +286,14 @@ __device__ __forceinline__ void first_check_phase(const uint2* __restrict__ plan
 // GT (large codes, N beyond what LDS holds): the bit totals live in global
 // scratch instead of LDS; everything else is the same kernel. The tables of
 // the QKD path (per-bit LDS indices) and the LDS-state min-sum are not used.
-template <int MODE, int RULE, int DC, bool CLAMP, bool GT>
+// ERA: the binary64 rule extended to zero LLRs (QKD_FLAG_ERASURES; edge_out);
+// kModeClass (qkd_reconcile_adaptive_batch, class bytes in the original bit
+// order) always has it.
+template <int MODE, int RULE, int DC, bool CLAMP, bool GT, bool ERA = false>
 __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
     using T = typename RuleMsg<RULE>::T;
+    static_assert(!ERA || RULE == kRuleSp64, "erasure rule: binary64");
+    static_assert(MODE != kModeClass || ERA, "class bytes: always with the erasure rule");
     // the exact QKD-path shortcuts (first/second-iteration tables) exist for
     // the reference rule only
     constexpr bool TABLES = MODE == kModeKeys && RULE == kRuleSp64 && !GT;
@@ -340,7 +345,10 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
 
     for (;;) {
         pc.mark(4);
-        if (tid == 0) ctl[0] = atomicAdd(a.counter, 1u);
+        if (tid == 0) {
+            ctl[0] = atomicAdd(a.counter, 1u);
+            if (MODE == kModeClass) ctl[1] = 0;      // the frame's payload flips
+        }
         for (int w = tid; w < m_words; w += kDecodeBlock) xsyn[w] = 0;
         __syncthreads();
         const uint32_t f = ctl[0];
@@ -372,6 +380,8 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
                 T l;
                 if (MODE == kModeLlr) {
                     l = (T)a.llr[(size_t)f * c.n + i];
+                } else if (MODE == kModeClass) {
+                    l = (T)class_llr(a.cls[(size_t)f * c.n + i], a.log_p, a.known);
                 } else {
                     const uint32_t bb = (uint32_t)((sw[a.words + (i >> 6)] >> (i & 63)) & 1u);
                     if (!GT) bobmask |= bb << r;
@@ -392,7 +402,7 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
             const int j = j0 + lane;
             const bool ok = j < c.m;
             int sj = 0, qj = 0;
-            if (MODE == kModeLlr) {
+            if (MODE == kModeLlr || MODE == kModeClass) {
                 sj = ok ? (a.syn[(size_t)f * c.m + j] != 0) : 0;
             } else {
                 // calculate_syndrome_irregular on Alice's key (:413-414), and
@@ -466,11 +476,13 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
             if constexpr (!MSL) {
                 if (!tabled) {
                     if (it == 0)
-                        check_phase<kSrcFirst, CLAMP, DC, RULE>(plan, tsyn, total, t2idx, tab2, c2b, row, n_tasks,
-                                                                n_pad, thr, wave, lane, a.ms_scale, a.ms_offset);
+                        check_phase<kSrcFirst, CLAMP, DC, RULE, ERA>(plan, tsyn, total, t2idx, tab2, c2b, row,
+                                                                     n_tasks, n_pad, thr, wave, lane, a.ms_scale,
+                                                                     a.ms_offset);
                     else
-                        check_phase<kSrcGeneral, CLAMP, DC, RULE>(plan, tsyn, total, t2idx, tab2, c2b, row,
-                                                                  n_tasks, n_pad, thr, wave, lane, a.ms_scale, a.ms_offset);
+                        check_phase<kSrcGeneral, CLAMP, DC, RULE, ERA>(plan, tsyn, total, t2idx, tab2, c2b, row,
+                                                                       n_tasks, n_pad, thr, wave, lane, a.ms_scale,
+                                                                       a.ms_offset);
                 }
             }
             __syncthreads();
@@ -509,6 +521,8 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
                     const int deg = dg[u];
                     T acc;
                     if (MODE == kModeLlr) acc = (T)a.llr[(size_t)f * c.n + i];
+                    else if (MODE == kModeClass)
+                        acc = (T)class_llr(a.cls[(size_t)f * c.n + i], a.log_p, a.known);
                     else if constexpr (GT)
                         acc = ((a.bob_w[(size_t)f * a.words + (i >> 6)] >> (i & 63)) & 1u) ? -llr_p : llr_p;
                     else
@@ -589,9 +603,18 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
 
         // ---- outputs: SP_result + last hard decision (+ keys_match)
         bool key_mismatch = false;
+        uint32_t nflip = 0;
         for (int i = tid; i < c.n; i += kDecodeBlock) {
             const uint8_t d = total[i] <= 0 ? 1 : 0;
             if (a.bits_out) a.bits_out[(size_t)f * c.n + i] = d;
+            if (MODE == kModeClass) {
+                // the payload of the decision and its flips against Bob's (class bit 0)
+                const int32_t k = a.src[i];
+                if (k >= 0) {
+                    a.payload_out[(size_t)f * a.n_payload + (uint32_t)k] = d;
+                    nflip += (uint32_t)(d ^ (a.cls[(size_t)f * c.n + i] & 1u));
+                }
+            }
             if (MODE == kModeKeys && !given) {
                 const uint64_t w = a.alice_w[(size_t)f * a.words + (i >> 6)];
                 key_mismatch |= (uint8_t)((w >> (i & 63)) & 1u) != d;
@@ -601,6 +624,11 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
             __syncthreads();
             const bool km = block_any(key_mismatch, ctl + 2, any_k);
             if (tid == 0 && a.key_ok) a.key_ok[f] = km ? 0 : 1;   // arrays_equal (:433)
+        }
+        if (MODE == kModeClass && a.flips) {
+            if (nflip) atomicAdd(ctl + 1, nflip);
+            __syncthreads();
+            if (tid == 0) a.flips[f] = ctl[1];
         }
         if (tid == 0) {
             a.iters[f] = done ? it + 1 : a.max_it;
@@ -1361,7 +1389,32 @@ static DecodeFn pick_decode_rule(int rule, bool clamp, int max_dc, int* dc) {
     return pick_decode_clamp<MODE, kRuleSp64, GT>(clamp, max_dc, dc);
 }
 
-static DecodeFn pick_decode(int mode, int rule, bool clamp, int max_dc, bool gt, int* dc) {
+// the erasure rule's kernels (binary64): the LLR path with QKD_FLAG_ERASURES
+// and the class-byte path
+template <int MODE, bool CLAMP, bool GT>
+static DecodeFn pick_decode_era_dc(int max_dc, int* dc) {
+    if constexpr (!GT) {
+        if (max_dc <= 4) { *dc = 4; return decode_kernel<MODE, kRuleSp64, 4, CLAMP, false, true>; }
+        if (max_dc <= 6) { *dc = 6; return decode_kernel<MODE, kRuleSp64, 6, CLAMP, false, true>; }
+        if (max_dc <= 8) { *dc = 8; return decode_kernel<MODE, kRuleSp64, 8, CLAMP, false, true>; }
+    }
+    if (max_dc <= 16) { *dc = 16; return decode_kernel<MODE, kRuleSp64, 16, CLAMP, GT, true>; }
+    *dc = 64;
+    return decode_kernel<MODE, kRuleSp64, 64, CLAMP, GT, true>;
+}
+template <int MODE>
+static DecodeFn pick_decode_era(bool clamp, int max_dc, bool gt, int* dc) {
+    if (gt)
+        return clamp ? pick_decode_era_dc<MODE, true, true>(max_dc, dc) : pick_decode_era_dc<MODE, false, true>(max_dc, dc);
+    return clamp ? pick_decode_era_dc<MODE, true, false>(max_dc, dc) : pick_decode_era_dc<MODE, false, false>(max_dc, dc);
+}
+
+static DecodeFn pick_decode(int mode, int rule, bool clamp, int max_dc, bool gt, int* dc, bool era = false) {
+    if (era || mode == kModeClass) {
+        if (rule != kRuleSp64 || mode == kModeKeys) return nullptr;
+        return mode == kModeClass ? pick_decode_era<kModeClass>(clamp, max_dc, gt, dc)
+                                  : pick_decode_era<kModeLlr>(clamp, max_dc, gt, dc);
+    }
     if (gt)
         return mode == kModeLlr ? pick_decode_rule<kModeLlr, true>(rule, clamp, max_dc, dc)
                                 : pick_decode_rule<kModeKeys, true>(rule, clamp, max_dc, dc);
@@ -1485,6 +1538,7 @@ static qkd_status ws_free(qkd_workspace* ws) {
     if (ws->win) (void)hipFree(ws->win);
     if (ws->ilv) (void)hipFree(ws->ilv);
     if (ws->fb_list) (void)hipFree(ws->fb_list);
+    if (ws->cls) (void)hipFree(ws->cls);
     if (ws->spec_stat_ev) (void)hipEventSynchronize(ws->spec_stat_ev);
     if (ws->spec_stat_host) (void)hipHostFree(ws->spec_stat_host);
     if (ws->spec_stat_ev) (void)hipEventDestroy(ws->spec_stat_ev);
@@ -1665,11 +1719,31 @@ static qkd_status check_no_static_lds(DecodeFn fn) {
 // frame, from the kernel that follows the decoder. verify
 // (qkd_reconcile_verify_batch, or nullptr): the frames' verification tags, from
 // that kernel too.
+// adapt (kModeClass, qkd_reconcile_adaptive_batch): the plan and Bob's payload;
+// the class bytes are written here, in the bit order of the kernel that runs.
 static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs& a, int mode,
                                 uint32_t flags, hipStream_t stream, uint32_t* corrected = nullptr,
-                                const VerifyArgs* verify = nullptr) {
+                                const VerifyArgs* verify = nullptr, const ClassArgs* adapt = nullptr) {
     int dc = 0;
     int rule = rule_of(flags);
+    // QKD_FLAG_ERASURES: the binary64 rule's erasure-aware instantiations,
+    // exact iterations only (the interval forms are not defined at t = 0), so
+    // the outputs cannot depend on QKD_SPEC_CAP. A dispatch without such an
+    // instantiation fails below; none applies the reference rule instead.
+    const bool era = (flags & QKD_FLAG_ERASURES) != 0 || mode == kModeClass;
+    if (era) {
+        if (rule != kRuleSp64 || mode == kModeKeys || a.trace || (mode == kModeClass && !adapt))
+            return set_error(QKD_ERR_UNSUPPORTED, "the erasure rule: binary64 variant, LLR or class entry, no trace");
+        a.spec_cap = 0;
+    }
+    // kModeClass: the class bytes of this launch, in the view's bit order
+    auto classes = [&](bool internal) -> hipError_t {
+        if (mode != kModeClass) return hipSuccess;
+        a.src = internal ? adapt->src_int : adapt->src_orig;
+        a.cls = adapt->cls;
+        return launch_adapt_classes(a.src, adapt->bob_payload, (uint32_t)c->n, a.n_payload, a.n_frames, adapt->cls,
+                                    stream);
+    };
     // QKD_MINSUM_STORE=global keeps the global-message-store min-sum (tests)
     // (QKD_MINSUM_STORE=lds keeps the LDS-state kernel: tests)
     const DbgOpt ms_store = debug_option(ws, "QKD_MINSUM_STORE");
@@ -1713,7 +1787,8 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
         const DecodeArgs a_in = a;
         int sdc = 0;
         DecodeFn sfn = long_code ? pick_split_long(a.clamp_on != 0, c->max_dc, &sdc)
-                                 : pick_split_decode(mode, rule, a.clamp_on != 0, c->max_dc, &sdc);
+                                 : pick_split_decode(mode, rule, a.clamp_on != 0, c->max_dc, &sdc, era);
+        if (!sfn) return set_error(QKD_ERR_UNSUPPORTED, "no split kernel with the erasure rule for this launch");
         const int esz = rule == kRuleSp64 ? 8 : 4;
         // diagnostic: QKD_SPLIT_BUDGET lowers the LDS budget (fewer LDS slots)
         size_t budget = kLdsBytesMax;
@@ -1950,6 +2025,7 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
                 QKD_HIP(launch_frame_syn(a, stream, debug_option(ws, "QKD_SYN_SLICED").is("0"),
                                          debug_option(ws, "QKD_SYN_BYTES").is("0")));
             } else {
+                QKD_HIP(classes(true));
                 QKD_HIP(hipMemsetAsync(ws->counter, 0, 8, stream));
                 if (a.win) QKD_HIP(hipMemsetAsync(a.win, 0, 2 * (size_t)a.win_count * sizeof(uint32_t), stream));
             }
@@ -2001,7 +2077,8 @@ classic_path:
         a.first_table = 0;
         a.tab2_entries = 0;
     }
-    DecodeFn fn = pick_decode(mode, rule, a.clamp_on != 0, c->max_dc, gt, &dc);
+    DecodeFn fn = pick_decode(mode, rule, a.clamp_on != 0, c->max_dc, gt, &dc, era);
+    if (!fn) return set_error(QKD_ERR_UNSUPPORTED, "no classic kernel with the erasure rule for this launch");
     const size_t lds = decode_lds_bytes(c, dc, a.tab2_entries, rule, gt, a.ms_sc != 0);
     int grid = 0;
     qkd_status s = decode_grid(c, fn, lds, &grid);
@@ -2012,6 +2089,7 @@ classic_path:
     s = ws_reserve_decode(ws, (rule == kRuleMinSumLds || rule == kRuleMinSumLdsSc) ? 0 : (size_t)grid);   // no global messages
     if (s != QKD_OK) return s;
     a.code = c->view();
+    QKD_HIP(classes(false));
     // (byte keys: the classic kernel reads them packed, in the original order)
     if (mode == kModeKeys && a.bob_b) QKD_HIP(launch_pack_keys(a, stream));
     a.c2b = ws->c2b;
@@ -2042,8 +2120,15 @@ static qkd_status check_frames(size_t n_frames) {
     return QKD_OK;
 }
 
-static qkd_status check_decode_params(uint32_t max_it, double thr, uint32_t flags) {
+// erasures_ok: the entry takes QKD_FLAG_ERASURES (qkd_decode_batch; binary64 variant only)
+static qkd_status check_decode_params(uint32_t max_it, double thr, uint32_t flags, bool erasures_ok = false) {
     if (max_it < 1) return set_error(QKD_ERR_INVALID_ARG, "max_iterations must be >= 1");
+    if (flags & QKD_FLAG_ERASURES) {
+        if (!erasures_ok) return set_error(QKD_ERR_INVALID_ARG, "QKD_FLAG_ERASURES is not taken by this entry");
+        if ((flags & QKD_VARIANT_MASK) != QKD_VARIANT_SP_F64)
+            return set_error(QKD_ERR_INVALID_ARG, "QKD_FLAG_ERASURES needs QKD_VARIANT_SP_F64");
+        flags &= ~QKD_FLAG_ERASURES;
+    }
     const uint32_t known = QKD_FLAG_THRESHOLD | QKD_VARIANT_MASK | (0xffu << QKD_MINSUM_SCALE_SHIFT) |
                            (0xffu << QKD_MINSUM_OFFSET_SHIFT) | QKD_MINSUM_SELF_CORRECT;
     if (flags & ~known) return set_error(QKD_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
@@ -2115,7 +2200,7 @@ qkd_status qkd_decode_batch(const qkd_code* c, qkd_workspace* ws, const double* 
     if (!c || !llr || !syndrome || !iterations || !syndromes_match)
         return set_error(QKD_ERR_INVALID_ARG, "null argument");
     qkd_status s = check_frames(n_frames);
-    if (s == QKD_OK) s = check_decode_params(max_iterations, msg_threshold, flags);
+    if (s == QKD_OK) s = check_decode_params(max_iterations, msg_threshold, flags, true);
     if (s != QKD_OK) return s;
     DeviceGuard g(c->device);
     ws = resolve_ws(c, ws);
@@ -2312,6 +2397,61 @@ qkd_status qkd_reconcile_batch(const qkd_code* c, qkd_workspace* ws, const uint8
         return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
     return reconcile_run(c, ws, bob, syndrome, n_frames, qber, max_iterations, msg_threshold, flags, bits_out,
                          iterations, syndromes_match, corrected, nullptr, stream);
+}
+
+qkd_status qkd_reconcile_adaptive_batch(const qkd_code* c, qkd_workspace* ws, const qkd_adapt* ad,
+                                        const uint8_t* bob_payload, const uint8_t* syndrome, size_t n_frames,
+                                        double qber, double known_llr, uint32_t max_iterations,
+                                        double msg_threshold, uint32_t flags, uint8_t* payload_out,
+                                        uint8_t* frames_out, uint32_t* iterations, uint8_t* syndromes_match,
+                                        uint32_t* corrected, void* stream) {
+    clear_error();
+    if (const char* bad = qkda::reconcile_args_error(c, bob_payload, syndrome, n_frames, qber, payload_out,
+                                                     iterations, syndromes_match))
+        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    if (!ad) return set_error(QKD_ERR_INVALID_ARG, "null argument");
+    if (ad->code != c) return set_error(QKD_ERR_INVALID_ARG, "the plan was created for another code");
+    if (!(known_llr > 0.0) || !std::isfinite(known_llr))
+        return set_error(QKD_ERR_INVALID_ARG, "known_llr must be finite and > 0");
+    // QKD_FLAG_ERASURES is implied; the decode parameters as qkd_reconcile_batch
+    qkd_status s = check_decode_params(max_iterations, msg_threshold, flags & ~QKD_FLAG_ERASURES);
+    if (s != QKD_OK) return s;
+    if ((flags & QKD_VARIANT_MASK) != QKD_VARIANT_SP_F64)
+        return set_error(QKD_ERR_UNSUPPORTED, "qkd_reconcile_adaptive_batch: QKD_VARIANT_SP_F64 only");
+    DeviceGuard g(c->device);
+    ws = resolve_ws(c, ws);
+    if (!ws) return set_error(QKD_ERR_OUT_OF_MEMORY, "no workspace");
+    WsSession sess(ws, (hipStream_t)stream);
+    // one class byte per bit and frame: the only per-bit input the decoder reads
+    const size_t need = n_frames * (size_t)c->n;
+    if (ws->cls_bytes < need) {
+        if (ws->cls) QKD_HIP(hipFree(ws->cls));
+        ws->cls = nullptr;
+        ws->cls_bytes = 0;
+        if (hipMalloc(&ws->cls, need) != hipSuccess)
+            return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of class bytes", need);
+        ws->cls_bytes = need;
+    }
+    DecodeArgs a{};
+    a.pinf = std::numeric_limits<float>::infinity();
+    a.n_frames = (uint32_t)n_frames;
+    a.max_it = max_iterations;
+    a.thr = msg_threshold;
+    a.clamp_on = (flags & QKD_FLAG_THRESHOLD) ? 1 : 0;
+    a.log_p = std::log((1. - qber) / qber);    // as qkd_reconcile_batch (decode_keys)
+    a.known = known_llr;
+    a.syn = syndrome;
+    a.bits_out = frames_out;
+    a.payload_out = payload_out;
+    a.n_payload = (uint32_t)ad->n_payload;
+    a.flips = corrected;
+    a.iters = iterations;
+    a.sp_ok = syndromes_match;
+    a.thr_dn = f32_bound(msg_threshold, false);
+    a.thr_up = f32_bound(msg_threshold, true);
+    const ClassArgs ca{ad->d_src_orig, ad->d_src_int, bob_payload, ws->cls};
+    return launch_decode(c, ws, a, kModeClass, flags & ~QKD_FLAG_ERASURES, (hipStream_t)stream, nullptr, nullptr,
+                         &ca);
 }
 
 static VerifyArgs verify_args(const qkd_code* c, uint64_t hash_seed, const uint64_t* hash_words, uint32_t tag_bits,

@@ -303,7 +303,7 @@ struct SplitStore {
 // task ahead are loaded before this task's arithmetic; stores trail by one
 // task. Slots of different tasks are distinct (idle lanes share the dummy
 // column's slot, whose value nothing reads).
-template <int SRC, bool CLAMP, int DC, int RULE, typename T, typename MS>
+template <int SRC, bool CLAMP, int DC, int RULE, bool ERA = false, typename T, typename MS>
 __device__ __forceinline__ void split_check_phase(const uint2* __restrict__ plan, const uint32_t* tsyn,
                                                   const double* tab2, const MS& ms, T* row,
                                                   int n_tasks, uint32_t n_pad, T thr, int wave, int lane) {
@@ -322,7 +322,7 @@ __device__ __forceinline__ void split_check_phase(const uint2* __restrict__ plan
         wave_lds_sync();
         // (edge_out reads the segment from a plan word of the unencoded form)
         const uint2 wo = make_uint2(w.x, ((uint32_t)seg_start(w) << 20) | ((uint32_t)(seg_deg<DC>(w) - 1) << 26));
-        return edge_out<CLAMP, DC, RULE>(a, wo, seg_sbit(w), lane, thr, row, 0.0f);
+        return edge_out<CLAMP, DC, RULE, ERA>(a, wo, seg_sbit(w), lane, thr, row, 0.0f);
     };
     uint2 wa = plan_word(prs, t, lane);
     uint2 wb = plan_word(prs, t + NW, lane);
@@ -1392,10 +1392,14 @@ template <class... A>
 constexpr bool sole_decode_args(void (*)(A...)) {
     return sizeof...(A) == 1 && (std::is_same<A, DecodeArgs>::value && ...);
 }
-template <int MODE, int RULE, int DC, bool CLAMP, int SPEC, bool LONG = false>
+// ERA: the binary64 rule extended to zero LLRs (QKD_FLAG_ERASURES; edge_out),
+// exact iterations only. kModeClass (qkd_reconcile_adaptive_batch) always has it.
+template <int MODE, int RULE, int DC, bool CLAMP, int SPEC, bool LONG = false, bool ERA = false>
 __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
-    static_assert(sole_decode_args(&decode_split_kernel<MODE, RULE, DC, CLAMP, SPEC, LONG>),
+    static_assert(sole_decode_args(&decode_split_kernel<MODE, RULE, DC, CLAMP, SPEC, LONG, ERA>),
                   "kernel_args(): DecodeArgs must be the only kernel parameter");
+    static_assert(!ERA || (RULE == kRuleSp64 && SPEC == 0 && !LONG), "erasure rule: binary64, exact iterations");
+    static_assert(MODE != kModeClass || ERA, "class bytes: always with the erasure rule");
     static_assert(!LONG || (MODE == kModeKeys && RULE == kRuleSp64 && SPEC == 0), "long codes: exact keys path");
     using T = typename RuleMsg<RULE>::T;
     // QKD path: the first check phase folds into the first bit phase for both
@@ -1654,6 +1658,9 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
                 T l;
                 if (MODE == kModeLlr) {
                     l = (T)a.llr[(size_t)f * c.n + c.perm[i]];
+                } else if (MODE == kModeClass) {
+                    // (class bytes are in the internal bit order: adapt_class_kernel)
+                    l = (T)class_llr(a.cls[(size_t)f * c.n + i], a.log_p, a.known);
                 } else {
                     const uint32_t bb = (uint32_t)((bw[i >> 6] >> (i & 63)) & 1u);
                     if (!LONG || r < 64) bobmask |= (uint64_t)bb << r;
@@ -1690,7 +1697,7 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
             }
         }
         // ---- prologue, LLR path: target syndrome bits per check (tsyn), thread per check
-        if (MODE == kModeLlr) {
+        if (MODE == kModeLlr || MODE == kModeClass) {
             for (int j0 = wave * 64; j0 < c.m; j0 += kDecodeBlock) {
                 const int j = j0 + lane;
                 const int sj = j < c.m ? (pa->syn[(size_t)f * c.m + j] != 0) : 0;
@@ -1801,8 +1808,8 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
                     split_check_phase<kSrcTable, CLAMP, DC, RULE>(plan, tsyn, tab2, ms, row, n_tasks, n_pad, thr,
                                                                    wave, lane);
                 else
-                    split_check_phase<kSrcFirst, CLAMP, DC, RULE>(plan, tsyn, tab2, ms, row, n_tasks, n_pad, thr,
-                                                                   wave, lane);
+                    split_check_phase<kSrcFirst, CLAMP, DC, RULE, ERA>(plan, tsyn, tab2, ms, row, n_tasks, n_pad,
+                                                                        thr, wave, lane);
                 __syncthreads();
             }
             pc.mark((FOLDS && it < 2 && fold1) ? 5 + (int)it : 1);
@@ -1880,6 +1887,8 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
                     const int deg = dg[u];
                     T acc;
                     if (MODE == kModeLlr) acc = ok ? (T)a.llr[(size_t)f * c.n + c.perm[i]] : (T)0;
+                    else if (MODE == kModeClass)
+                        acc = ok ? (T)class_llr(a.cls[(size_t)f * c.n + i], a.log_p, a.known) : (T)0;
                     else acc = bob_r(r) ? -llr_p : llr_p;
                     if constexpr (FOLDS) if (folded && ok) {
                         // fold_first_message: message of the k-th check j of bit i is
@@ -2065,6 +2074,22 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
             // (zout_unpack_kernel puts the bits back in place)
             if (ea->bits_out)
                 for (int q = etid; q < (int)ea->words; q += kDecodeBlock) ea->zout[(size_t)f * ea->words + q] = zw[q];
+        } else if (MODE == kModeClass) {
+            // the payload of the decision (bit i's payload index: src[i], < 0
+            // for punctured and shortened bits), its flips against Bob's
+            // payload (class bit 0) summed through ctl[7], and the whole
+            // decision where asked for
+            uint32_t nflip = 0;
+            for (int i = etid; i < c.n; i += kDecodeBlock) {
+                const uint8_t z = (uint8_t)((zw[i >> 6] >> (i & 63)) & 1u);
+                const int32_t k = ea->src[i];
+                if (k >= 0) {
+                    ea->payload_out[(size_t)f * ea->n_payload + (uint32_t)k] = z;
+                    nflip += (uint32_t)(z ^ (ea->cls[(size_t)f * c.n + i] & 1u));
+                }
+                if (ea->bits_out) ea->bits_out[(size_t)f * c.n + c.perm[i]] = z;
+            }
+            if (ea->flips && nflip) atomicAdd(ctl + 7, nflip);
         } else if (ea->bits_out) {
             for (int i = etid; i < c.n; i += kDecodeBlock)
                 ea->bits_out[(size_t)f * c.n + c.perm[i]] = (uint8_t)((zw[i >> 6] >> (i & 63)) & 1u);
@@ -2085,6 +2110,10 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
         __syncthreads();
         if (MODE == kModeKeys && ea->key_ok && tid == 0) {
             ea->key_ok[f] = ctl[7] ? 0 : 1;
+            ctl[7] = 0;
+        }
+        if (MODE == kModeClass && ea->flips && tid == 0) {
+            ea->flips[f] = ctl[7];
             ctl[7] = 0;
         }
     }
@@ -2828,7 +2857,27 @@ DecodeFn pick_split_long(bool clamp, int max_dc, int* dc) {
                  : decode_split_kernel<kModeKeys, kRuleSp64, 16, false, 0, true>;
 }
 
-DecodeFn pick_split_decode(int mode, int rule, bool clamp, int max_dc, int* dc) {
+// the erasure rule's kernels (binary64, exact iterations): the LLR path with
+// QKD_FLAG_ERASURES, and the class-byte path
+template <int MODE, bool CLAMP>
+static DecodeFn pick_split_era_dc(int max_dc, int* dc) {
+    if (max_dc <= 4) { *dc = 4; return decode_split_kernel<MODE, kRuleSp64, 4, CLAMP, 0, false, true>; }
+    if (max_dc <= 6) { *dc = 6; return decode_split_kernel<MODE, kRuleSp64, 6, CLAMP, 0, false, true>; }
+    if (max_dc <= 8) { *dc = 8; return decode_split_kernel<MODE, kRuleSp64, 8, CLAMP, 0, false, true>; }
+    if (max_dc <= 16) { *dc = 16; return decode_split_kernel<MODE, kRuleSp64, 16, CLAMP, 0, false, true>; }
+    *dc = 64;
+    return decode_split_kernel<MODE, kRuleSp64, 64, CLAMP, 0, false, true>;
+}
+
+DecodeFn pick_split_decode(int mode, int rule, bool clamp, int max_dc, int* dc, bool era) {
+    if (era || mode == kModeClass) {
+        if (rule != kRuleSp64) return nullptr;
+        if (mode == kModeClass)
+            return clamp ? pick_split_era_dc<kModeClass, true>(max_dc, dc)
+                         : pick_split_era_dc<kModeClass, false>(max_dc, dc);
+        if (mode != kModeLlr) return nullptr;
+        return clamp ? pick_split_era_dc<kModeLlr, true>(max_dc, dc) : pick_split_era_dc<kModeLlr, false>(max_dc, dc);
+    }
     return mode == kModeLlr ? pick_split_rule<kModeLlr>(rule, clamp, max_dc, dc)
                             : pick_split_rule<kModeKeys>(rule, clamp, max_dc, dc);
 }

@@ -828,6 +828,51 @@ qkd_status qkd_debug_bit_order(int32_t n, int32_t m, const int32_t* cptr, const 
     return QKD_OK;
 }
 
+qkd_status qkd_adapt_positions(int32_t n, int32_t m, const int32_t* cptr, const int32_t* cidx, int32_t count,
+                               uint64_t seed, int32_t* positions, int32_t* untainted_out) {
+    clear_error();
+    std::vector<int32_t> bdeg;
+    int32_t max_dc = 0;
+    const qkd_status vs = validate_csr(n, m, cptr, cidx, bdeg, max_dc);
+    if (vs != QKD_OK) return vs;
+    if (count < 0 || count > n || (count > 0 && !positions))
+        return set_error(QKD_ERR_INVALID_ARG, "qkd_adapt_positions: count %d outside [0, %d] or null output", count, n);
+    // the candidates' order: Fisher-Yates from the top, draw k = R[k] of the seeded string
+    std::vector<int32_t> order(n);
+    for (int32_t i = 0; i < n; ++i) order[i] = i;
+    uint64_t k = 0;
+    for (int32_t i = n - 1; i >= 1; --i, ++k) {
+        const uint64_t j = qkdv::verify_key_word(seed, k) % (uint64_t)(i + 1);
+        std::swap(order[i], order[(size_t)j]);
+    }
+    // bit-side lists: the checks of each bit
+    std::vector<int32_t> bptr(n + 1, 0), bidx(cptr[m]), fill(n, 0);
+    for (int32_t i = 0; i < n; ++i) bptr[i + 1] = bptr[i] + bdeg[i];
+    for (int32_t j = 0; j < m; ++j)
+        for (int32_t e = cptr[j]; e < cptr[j + 1]; ++e) bidx[bptr[cidx[e]] + fill[cidx[e]]++] = j;
+    // pass 1: candidates none of whose checks touches an earlier pick
+    std::vector<uint8_t> tainted(m, 0), taken(n, 0);
+    int32_t got = 0;
+    for (int32_t t = 0; t < n && got < count; ++t) {
+        const int32_t b = order[t];
+        bool free_ = true;
+        for (int32_t e = bptr[b]; e < bptr[b + 1]; ++e) free_ = free_ && !tainted[bidx[e]];
+        if (!free_) continue;
+        for (int32_t e = bptr[b]; e < bptr[b + 1]; ++e) tainted[bidx[e]] = 1;
+        taken[b] = 1;
+        positions[got++] = b;
+    }
+    if (untainted_out) *untainted_out = got;
+    // pass 2: the untaken candidates in the same order
+    for (int32_t t = 0; t < n && got < count; ++t) {
+        const int32_t b = order[t];
+        if (taken[b]) continue;
+        taken[b] = 1;
+        positions[got++] = b;
+    }
+    return QKD_OK;
+}
+
 qkd_status qkd_make_seeds(uint64_t simulation_seed, size_t count, uint64_t* seeds) {
     if (count && !seeds) return set_error(QKD_ERR_INVALID_ARG, "null seeds");
     qkdr::Xoshiro256pp g;

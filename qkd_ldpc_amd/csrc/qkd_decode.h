@@ -40,7 +40,12 @@ constexpr int kFirstTableDeg = 16;
 
 enum DecodeMode : int {
     kModeLlr = 0,  // qkd_decode_batch: caller LLRs + syndrome bytes
-    kModeKeys = 1  // QKD_LDPC path: packed alice/bob keys, LLR = +-log_p
+    kModeKeys = 1, // QKD_LDPC path: packed alice/bob keys, LLR = +-log_p
+    // qkd_reconcile_adaptive_batch: one class byte per bit (DecodeArgs::cls, in
+    // the launched kernel's bit order) and the caller's syndrome bytes; the LLR
+    // of a bit is the level of its class: 0 +log_p, 1 -log_p, 2 +0.0
+    // (punctured), 3 +known (shortened). Always with the erasure rule.
+    kModeClass = 2
 };
 
 // Check-node rule and message width (QKD_VARIANT_* in qkd_ldpc.h).
@@ -204,7 +209,25 @@ struct DecodeArgs {
     // interleaved decoder's hand-offs), or every frame when nullptr
     const uint32_t* frame_list;
     const uint32_t* frame_count;
+    // kModeClass: the frames' class bytes (F x N, the launched view's bit
+    // order), the shortened bits' LLR, and the payload outputs: src[i] = the
+    // payload index of the view's bit i (< 0: punctured or shortened),
+    // payload_out F x n_payload, flips[f] = popcount(payload_out ^ bob's
+    // payload) or nullptr. bits_out (may be nullptr): the whole decision.
+    const uint8_t* cls;
+    double known;
+    const int32_t* src;
+    uint8_t* payload_out;
+    uint32_t n_payload;
+    uint32_t* flips;
 };
+
+// kModeClass: the channel LLR of a class byte (selects on registers: no table)
+__device__ __forceinline__ double class_llr(uint32_t cl, double log_p, double known) {
+    const double a = (cl & 1u) ? -log_p : log_p;
+    const double b = (cl & 1u) ? known : 0.0;
+    return (cl & 2u) ? b : a;
+}
 
 // The frame-interleaved decoder (decode_ilv.hip): kIlvCols frames per
 // workgroup in lockstep, one per lane of each 16-lane group; one message
@@ -488,7 +511,13 @@ __device__ __forceinline__ T edge_in(T x, T old, T thr) {
 // Second half: the lane's message from the published row of its check
 // (segment [start, start + deg) of `row`; the row has 64 + DC entries, so reads
 // past a segment's end stay inside it and are discarded).
-template <bool CLAMP, int DC, int RULE, typename T>
+// ERA (QKD_FLAG_ERASURES, binary64 rule): the rule extended to published
+// values that are zero. With z = the number of zero t_k of the check (either
+// sign): z = 0 the reference rule; z = 1 the edge whose t is zero gets
+// 2 atanh(P'), P' the product without it (same order), every other edge +0.0;
+// z >= 2 every edge +0.0. A frame without a zero t computes what the reference
+// rule computes, operation for operation.
+template <bool CLAMP, int DC, int RULE, bool ERA = false, typename T>
 __device__ __forceinline__ T edge_out(T tv, uint2 w, uint32_t sbit, int lane, T thr, const T* row,
                                       float ms_scale, float ms_offset = 0.0f) {
     const int start = pw_start(w);
@@ -514,10 +543,24 @@ __device__ __forceinline__ T edge_out(T tv, uint2 w, uint32_t sbit, int lane, T 
     } else if constexpr (RULE == kRuleSp64) {
         // the reference's P = (s_j ? -1 : 1) * prod_k t_k, then 2 atanh(P / t_self) (:231-241)
         T P = sbit ? (T)-1 : (T)1;
-        P = P * o[0];                         // every check has degree >= 1
+        if constexpr (ERA) {
+            int z = 0;
 #pragma unroll
-        for (int k = 1; k < DC; ++k) P = k < deg ? P * o[k] : P;
-        v = RuleMath<RULE>::two_atanh(P / tv);
+            for (int k = 0; k < DC; ++k) {
+                if (k < deg) {
+                    const bool zero = o[k] == (T)0;
+                    z += zero ? 1 : 0;
+                    P = zero ? P : P * o[k];
+                }
+            }
+            v = RuleMath<RULE>::two_atanh(z == 0 ? P / tv : P);
+            if (z >= 2 || (z == 1 && !(tv == (T)0))) v = (T)0;
+        } else {
+            P = P * o[0];                         // every check has degree >= 1
+#pragma unroll
+            for (int k = 1; k < DC; ++k) P = k < deg ? P * o[k] : P;
+            v = RuleMath<RULE>::two_atanh(P / tv);
+        }
     } else {
         // binary32 variant (Gallager form, RuleMath<kRuleSp32>): the extrinsic
         // psi sum over the other edges in ascending order and their sign parity
@@ -710,7 +753,8 @@ __host__ __device__ inline size_t cl_words_offset(int n_tasks, int rem_tasks) {
 using DecodeFn = void (*)(DecodeArgs);
 // decode_split.hip: the split-store kernel for (mode, rule in {kRuleSp64,
 // kRuleSp32}, clamp, check-degree bucket); *dc receives the bucket.
-DecodeFn pick_split_decode(int mode, int rule, bool clamp, int max_dc, int* dc);
+// era (binary64 rule, kModeLlr; kModeClass always): the erasure rule's kernels.
+DecodeFn pick_split_decode(int mode, int rule, bool clamp, int max_dc, int* dc, bool era = false);
 // the exact keys-path split kernel for codes past kMaxBitsSplit bits (up to
 // kMaxBitsSplitLong; check degree <= 16): the interleaved decoder's hand-offs
 DecodeFn pick_split_long(bool clamp, int max_dc, int* dc);
@@ -742,5 +786,19 @@ hipError_t launch_count_flips(const uint8_t* bits, const uint8_t* bob, uint32_t 
 // qkd_reconcile_verify_batch after the classic kernel): one launch, no workspace
 hipError_t launch_verify_tags(const uint8_t* bits, uint32_t n, uint32_t n_frames, const VerifyArgs& v,
                               hipStream_t stream);
+// adapt.hip, kModeClass: what launch_decode needs of a qkd_adapt and its call
+// (the plan's maps in both bit orders, Bob's payload, the workspace's class
+// bytes), and the kernel that writes the class bytes of F frames from a map:
+// cls[f * n + i] = src[i] >= 0 ? payload[f * n_payload + src[i]] & 1
+//                              : src[i] == kSrcPunctured ? 2 : 3
+struct ClassArgs {
+    const int32_t* src_orig;
+    const int32_t* src_int;
+    const uint8_t* bob_payload;
+    uint8_t* cls;
+};
+constexpr int32_t kSrcPunctured = -1, kSrcShortened = -2;
+hipError_t launch_adapt_classes(const int32_t* src, const uint8_t* payload, uint32_t n, uint32_t n_payload,
+                                uint32_t n_frames, uint8_t* cls, hipStream_t stream);
 
 }  // namespace qkd

@@ -199,6 +199,9 @@ struct qkd_workspace {
     size_t ilv_elems = 0;
     uint32_t* fb_list = nullptr;
     size_t fb_frames = 0;
+    // qkd_reconcile_adaptive_batch: one class byte per bit and frame (adapt.hip)
+    uint8_t* cls = nullptr;
+    size_t cls_bytes = 0;
     // qkd_debug_decoder_timing: while on, HIP events bracket every decoder
     // launch on its stream (pairs recorded, read back on collection)
     bool time_decoder = false;
@@ -291,6 +294,24 @@ struct qkd_code {
                                n_pat, d_bit_pat_s, d_pat_deg, d_bit_code, d_plan_slot, d_perm, d_inv,
                                d_chk_rows16, chk_rs, d_ilv_slots, ilv_rs, d_chk_odd};
     }
+};
+
+// A rate-adaptation plan (adapt.hip): which bits of a frame are punctured,
+// shortened or payload. Immutable after creation, shareable like a code.
+//   d_src_orig[i]  original bit i: its payload index k >= 0 (payload bit k is
+//                  the k-th position, ascending, that is neither punctured nor
+//                  shortened), or kSrcPunctured / kSrcShortened (qkd_decode.h)
+//   d_src_int[q]   the same for the split kernels' internal bit q (perm[q])
+//   d_emb[i]       embedding: the payload index k >= 0, -1 for a shortened bit,
+//                  -2 - r for the punctured bit that takes fill byte r (the
+//                  r-th of the caller's punctured list)
+struct qkd_adapt {
+    const qkd_code* code = nullptr;
+    int device = 0;
+    int32_t n = 0, n_payload = 0, p = 0, s = 0;
+    int32_t* d_src_orig = nullptr;
+    int32_t* d_src_int = nullptr;
+    int32_t* d_emb = nullptr;
 };
 
 namespace qkd {
