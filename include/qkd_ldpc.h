@@ -18,7 +18,12 @@
  * guarded by a mutex and therefore serialises such calls at the host (calls
  * on different streams then must not overlap on the device: they are
  * ordered by an internal event). For concurrent streams create one
- * workspace per stream.
+ * workspace per stream. Stream capture: a call of any entry on a stream that
+ * is being captured neither waits on nor records that event (a captured
+ * record would tie later, uncaptured calls to the capture), so a graph holds
+ * the call's own work only; the caller orders the graph's replays against
+ * every other use of the same workspace, most simply by replaying on the one
+ * stream that uses it.
  *
  * Errors: no exception crosses this boundary. Every call returns a
  * qkd_status; qkd_last_error() returns a thread-local message for the most
@@ -364,6 +369,71 @@ QKD_API qkd_status qkd_reconcile_adaptive_batch(const qkd_code *code, qkd_worksp
                                                 uint32_t max_iterations, double msg_threshold, uint32_t flags,
                                                 uint8_t *payload_out, uint8_t *frames_out, uint32_t *iterations,
                                                 uint8_t *syndromes_match, uint32_t *corrected, void *stream);
+
+/* Blind reconciliation (Martinez-Mateo et al.): rate adaptation made
+ * interactive. Alice sends one syndrome; Bob decodes; for the frames that fail,
+ * Alice discloses the values of the next punctured bits, in the order of the
+ * plan's punctured list, and Bob decodes those frames again with these
+ * positions as known bits instead of erasures. No new syndrome, no QBER
+ * estimate, and each frame stops at its own rate.
+ *
+ * revealed[F * p]: byte f * p + j is the value (byte & 1) of frame f's punctured
+ * bit of rank j, the j-th of the plan's punctured list, i.e. Alice's fill byte
+ * (qkd_adapt_embed_batch). n_revealed[F], in/out: how many of them Bob holds for
+ * frame f. The call never reads revealed[f * p + j] for j >= n_revealed[f].
+ * skip[F] (may be NULL), rounds[F] (may be NULL); the other arguments as
+ * qkd_reconcile_adaptive_batch. All arrays on the plan's device.
+ *
+ *  - Skipped frames. A frame with skip[f] != 0 is not decoded and none of its
+ *    outputs is written (n_revealed[f] and rounds[f] included).
+ *  - Rounds. The other frames are open at round 0. In round
+ *    t = 0 .. max_rounds-1 every open frame is decoded.
+ *  - Decision. The N-bit decision, iterations and syndromes_match equal what
+ *    qkd_decode_batch returns with flags | QKD_FLAG_ERASURES for the LLRs
+ *      payload position holding Bob's bit b:      b ? -log_p : +log_p
+ *      shortened position:                        +known_llr
+ *      punctured position of rank j < min(n_revealed[f], p):
+ *                                  revealed[f * p + j] & 1 ? -known_llr : +known_llr
+ *      other punctured position:                  +0.0
+ *  - Outputs. The frame's outputs are overwritten with this round's;
+ *    corrected[f] = popcount(payload_out ^ bob_payload) as before.
+ *  - Closing a frame. A frame that matched is closed. So is a frame that
+ *    failed with n_revealed[f] >= p: it has nothing more to reveal and is not
+ *    decoded again on the same input.
+ *  - Advancing a frame. A frame that failed with bits left, while another
+ *    round follows, gets n_revealed[f] = min(p, n_revealed[f] + step). On
+ *    return n_revealed[f] is therefore the count its last decode used.
+ *  - rounds[f]: how many rounds decoded frame f; written for every frame that
+ *    is not skipped.
+ *  - n_revealed[f] > p on entry counts as p (and is returned as p).
+ *  - max_rounds = 1 is Bob's step on a real link: he decodes with what he
+ *    has, asks Alice for more, and calls again with skip set for the frames
+ *    that are done. step is then not used.
+ *  - max_rounds > 1: revealed holds Alice's whole fill; the simulation and
+ *    benchmark form, as qkd_trials_batch is for the fixed-rate path.
+ *  - Zero reveals. With n_revealed all 0, skip NULL and max_rounds = 1 the
+ *    call returns exactly what qkd_reconcile_adaptive_batch returns.
+ *
+ * Validated before any device work: everything qkd_reconcile_adaptive_batch
+ * validates; max_rounds >= 1; step >= 1 when max_rounds > 1; n_revealed not
+ * NULL; revealed not NULL exactly when p > 0. Only QKD_VARIANT_SP_F64
+ * (otherwise QKD_ERR_UNSUPPORTED); exact iterations only.
+ *
+ * A round is three kernels on the stream: one that settles the round before
+ * and lists the open frames, one that writes their class bytes (classes 4 and
+ * 5: a revealed 0 and a revealed 1), and the decoder, at its usual grid, over
+ * that list; a workgroup that finds the list exhausted exits. The host never
+ * reads the list's length: no synchronisation, no host copy, no allocation
+ * beyond the workspace's grow-on-demand; capturable once the workspace has its
+ * size (see "Stream capture" at the top for the workspace's ordering then). */
+QKD_API qkd_status qkd_reconcile_blind_batch(const qkd_code *code, qkd_workspace *ws, const qkd_adapt *adapt,
+                                             const uint8_t *bob_payload, const uint8_t *syndrome, size_t n_frames,
+                                             double qber, double known_llr, uint32_t max_iterations,
+                                             double msg_threshold, uint32_t flags, const uint8_t *revealed,
+                                             uint32_t *n_revealed, const uint8_t *skip, uint32_t step,
+                                             uint32_t max_rounds, uint8_t *payload_out, uint8_t *frames_out,
+                                             uint32_t *iterations, uint8_t *syndromes_match, uint32_t *corrected,
+                                             uint32_t *rounds, void *stream);
 
 /* ---- privacy amplification --------------------------------------------------
  * The last step before a secret key: the corrected (and verified) key is

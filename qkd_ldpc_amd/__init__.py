@@ -16,6 +16,7 @@ src/array_and_matrix_operations.hpp) with batched, device-resident arrays:
   (no counterpart) privacy amplification            privacy_amplify(keys, out_bits, ..., keep=verified)
   (no counterpart) punctured / shortened frames     AdaptPlan, adapt_embed, adapt_extract,
                                                     reconcile_adaptive(H, plan, bob_payload, ...)
+  (no counterpart) blind reconciliation             reconcile_blind(H, plan, bob_payload, ..., revealed=)
   generate_random_bit_array + introduce_errors    keygen(H, seeds, q_nominal, ...)
   run_trial over a batch + the batch reduction    run_trials(H, seeds, q_nominal, ...)
   seeds of QKD_LDPC_batch_simulation              make_seeds(simulation_seed, count)
@@ -49,6 +50,7 @@ __all__ = [
     "verify_key_words", "verify_expand_key", "verify_tags",
     "privacy_key_words", "privacy_expand_key", "privacy_amplify",
     "AdaptPlan", "adapt_positions", "adapt_embed", "adapt_extract", "reconcile_adaptive",
+    "reconcile_blind", "BlindResult",
 ]
 
 
@@ -101,6 +103,16 @@ def _stream(stream, device: int) -> int | None:
     if isinstance(stream, int):
         return stream
     return int(stream.cuda_stream)
+
+
+def _torch_stream(stream, device: int):
+    """The launch stream of _stream(stream, device) as a torch stream, for a wrapper's own
+    torch work (an int is a raw stream handle, 0 the null stream)."""
+    if stream is None:
+        return torch.cuda.current_stream(device)
+    if isinstance(stream, int):
+        return torch.cuda.ExternalStream(stream, device=device)
+    return stream
 
 
 def _need_cuda(t, dtype, name, H: "HMatrix | None" = None):
@@ -594,6 +606,83 @@ def reconcile_adaptive(H: HMatrix, plan: AdaptPlan, bob_payload, syndrome, qber:
         max_iterations, msg_threshold, flags, _ptr(bits), _ptr(frames), _ptr(iters), _ptr(ok), _ptr(corrected),
         _stream(stream, H.device)))
     return ReconcileResult(iters, ok, bits, corrected, frames=frames)
+
+
+@dataclass
+class BlindResult(ReconcileResult):
+    """reconcile_blind's view of its frames: ReconcileResult's fields (a skipped frame's
+    entries are left as allocated, never written), rounds (how many rounds decoded the
+    frame), n_revealed (the revealed-bit count its last decode used) and leak_bits =
+    M - p + n_revealed, the key bits the exchange disclosed for that frame, which the
+    caller takes off in privacy amplification (all int32, on the device)."""
+    rounds: "torch.Tensor | None" = None
+    n_revealed: "torch.Tensor | None" = None
+    leak_bits: "torch.Tensor | None" = None
+
+
+def reconcile_blind(H: HMatrix, plan: AdaptPlan, bob_payload, syndrome, qber: float,
+                    revealed=None, n_revealed=None, skip=None, step: int = 0, max_rounds: int = 1,
+                    known_llr: float = 100.0, max_iterations: int = 50, msg_threshold: float = 100.0,
+                    threshold_enabled: bool = True, want_corrected: bool = True,
+                    want_frames: bool = False, workspace=None, stream=None) -> BlindResult:
+    """Blind reconciliation, Bob's side (qkd_reconcile_blind_batch): reconcile_adaptive
+    made interactive. revealed [F, p] uint8: the values (byte & 1) of the punctured bits in
+    the order of the plan's punctured list, i.e. Alice's fill, of which frame f holds the
+    first n_revealed[f] ([F] int32; missing: zeros; the caller's tensor is not modified);
+    those positions are known bits (LLR -+known_llr) instead of erasures, and no later byte
+    of `revealed` is read. skip [F] uint8: nonzero = the frame is left alone, outputs
+    included. In each of max_rounds rounds every open frame is decoded; one that matched is
+    closed, as is one with nothing left to reveal; any other gets `step` more bits for the
+    next round. max_rounds = 1 is Bob's step on a link (he then asks Alice for more and
+    calls again with skip set for the finished frames); max_rounds > 1 wants Alice's whole
+    fill and runs the rounds on the device without a trip to the host. With no reveals, no
+    skip and one round the result is reconcile_adaptive's.
+
+    The counts are uint32 in the library and a count past p counts as p, so a negative
+    int32 count means "everything revealed" (it cannot be rejected without a
+    synchronisation). With stream= given, the copy of n_revealed and leak_bits are made on
+    that stream too, after whatever it already holds: the inputs must be ready there, and
+    the result is ready once that stream is."""
+    _need_cuda(bob_payload, torch.uint8, "bob_payload", H)
+    _need_cuda(syndrome, torch.uint8, "syndrome", H)
+    f = _frames(bob_payload, plan.n_payload, "bob_payload")
+    _frames(syndrome, H.num_check_nodes, "syndrome", f)
+    p = plan.n_punctured
+    if revealed is not None:
+        _need_cuda(revealed, torch.uint8, "revealed", H)
+        if p == 0:
+            raise QkdError(N.ERR_INVALID_ARG, "revealed given for a plan without punctured positions")
+        _frames(revealed, p, "revealed", f)
+    elif p > 0:
+        raise QkdError(N.ERR_INVALID_ARG, "revealed is required when the plan punctures")
+    dev = bob_payload.device
+    if n_revealed is not None:
+        _need_vec(n_revealed, torch.int32, f, "n_revealed", H)
+    if skip is not None:
+        _need_vec(skip, torch.uint8, f, "skip", H)
+    if not (isinstance(max_rounds, int) and 1 <= max_rounds < 2**32):
+        raise QkdError(N.ERR_INVALID_ARG, "max_rounds must be >= 1")
+    if not (isinstance(step, int) and 0 <= step < 2**32) or (max_rounds > 1 and step < 1):
+        raise QkdError(N.ERR_INVALID_ARG, "step must be >= 1 when max_rounds > 1")
+    bits = torch.empty((f, plan.n_payload), dtype=torch.uint8, device=dev)
+    frames = torch.empty((f, H.num_bit_nodes), dtype=torch.uint8, device=dev) if want_frames else None
+    iters = torch.empty(f, dtype=torch.int32, device=dev)
+    ok = torch.empty(f, dtype=torch.uint8, device=dev)
+    corrected = torch.empty(f, dtype=torch.int32, device=dev) if want_corrected else None
+    rounds = torch.empty(f, dtype=torch.int32, device=dev)
+    flags = decoder_flags(threshold_enabled, "sp_f64")
+    # The copy of the counts before the call and leak_bits after it are torch work of this
+    # wrapper: they go on the launch stream, where the kernels that read and advance the
+    # counts run, not on whatever stream is current.
+    with torch.cuda.stream(_torch_stream(stream, H.device)):
+        nrev = torch.zeros(f, dtype=torch.int32, device=dev) if n_revealed is None else n_revealed.clone()
+        N.check(N.lib().qkd_reconcile_blind_batch(
+            H.handle, _ws(workspace), plan.handle, _ptr(bob_payload), _ptr(syndrome), f, qber, known_llr,
+            max_iterations, msg_threshold, flags, _ptr(revealed), _ptr(nrev), _ptr(skip), step, max_rounds,
+            _ptr(bits), _ptr(frames), _ptr(iters), _ptr(ok), _ptr(corrected), _ptr(rounds),
+            _stream(stream, H.device)))
+        leak = nrev + (H.num_check_nodes - p)
+    return BlindResult(iters, ok, bits, corrected, frames=frames, rounds=rounds, n_revealed=nrev, leak_bits=leak)
 
 
 class _Device:

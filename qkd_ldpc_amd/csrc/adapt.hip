@@ -1,7 +1,8 @@
 // adapt.hip — rate adaptation of one mother code by puncturing and shortening
 // (Elkouss et al.): the plan object (qkd_adapt), the kernels that place a
 // payload in a frame and take it out again, and the class bytes the decoder of
-// qkd_reconcile_adaptive_batch reads instead of per-bit LLRs.
+// qkd_reconcile_adaptive_batch reads instead of per-bit LLRs, and the round
+// kernels of qkd_reconcile_blind_batch (revealed punctured bits, per frame).
 //
 // A frame of N bits holds n_payload = N - p - s key bits (payload bit k at the
 // k-th position, ascending, that is neither punctured nor shortened), p
@@ -30,6 +31,87 @@ __global__ __launch_bounds__(kAdaptBlock) void adapt_class_kernel(const int32_t*
     if (k >= 0) v = payload[f * n_payload + (uint32_t)k] & 1u;
     else v = k == kSrcPunctured ? 2u : 3u;
     cls[f * n + i] = v;
+}
+
+// qkd_reconcile_blind_batch: the same for frame f = list[blockIdx.y] of the
+// round's open frames, with the punctured bits Alice has revealed so far as
+// known bits: rank[i] = j is position i's index in the plan's punctured list
+// (-1 elsewhere), and the position is class 4 | value when j < min(nrev[f], p).
+// revealed[f * p + j] is read for those j only: Bob has no later byte yet.
+__global__ __launch_bounds__(kAdaptBlock) void blind_class_kernel(const int32_t* __restrict__ src,
+                                                                  const int32_t* __restrict__ rank,
+                                                                  const uint8_t* __restrict__ payload,
+                                                                  const uint8_t* __restrict__ revealed,
+                                                                  const uint32_t* __restrict__ nrev,
+                                                                  const uint32_t* __restrict__ list,
+                                                                  const uint32_t* __restrict__ count, uint32_t y0,
+                                                                  uint32_t n, uint32_t n_payload, uint32_t p,
+                                                                  uint8_t* __restrict__ cls) {
+    const uint32_t k = y0 + blockIdx.y;
+    if (k >= *count) return;
+    const uint32_t i = blockIdx.x * kAdaptBlock + threadIdx.x;
+    if (i >= n) return;
+    const size_t f = list[k];
+    const int32_t s = src[i];
+    uint8_t v;
+    if (s >= 0) {
+        v = payload[f * n_payload + (uint32_t)s] & 1u;
+    } else if (s == kSrcPunctured) {
+        const uint32_t nr = nrev[f] < p ? nrev[f] : p;
+        const uint32_t j = (uint32_t)rank[i];
+        v = j < nr ? (uint8_t)(4u | (revealed[f * p + j] & 1u)) : (uint8_t)2u;
+    } else {
+        v = 3u;
+    }
+    cls[f * n + i] = v;
+}
+
+// One round's bookkeeping of qkd_reconcile_blind_batch (BlindRound), one
+// workgroup. Round 0 opens every frame that is not skipped (n_revealed past p
+// counts as p, rounds = 0). A later round first settles the frames the round
+// before decoded: a frame that matched is closed, so is one that failed with
+// nothing left to reveal; any other gets step more bits, up to p. Then the
+// open frames go to list in ascending order (rounds[f] counts the rounds that
+// decode f) and *count says how many.
+constexpr int kBlindBlock = 1024;
+__global__ __launch_bounds__(kBlindBlock) void blind_round_kernel(BlindRound r) {
+    __shared__ uint32_t wave_n[kBlindBlock / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t total = 0;
+    for (uint32_t f0 = 0; f0 < r.n_frames; f0 += kBlindBlock) {       // (uniform trip count)
+        const uint32_t f = f0 + tid;
+        bool open = false;
+        if (f < r.n_frames) {
+            if (r.round == 0) {
+                open = !(r.skip && r.skip[f] != 0);
+                if (open) {
+                    if (r.n_revealed[f] > r.p) r.n_revealed[f] = r.p;
+                    if (r.rounds) r.rounds[f] = 0;
+                }
+            } else if (r.open[f]) {
+                const uint32_t nr = r.n_revealed[f];
+                open = r.sp_ok[f] == 0 && nr < r.p;
+                if (open) r.n_revealed[f] = r.step >= r.p - nr ? r.p : nr + r.step;
+            }
+            r.open[f] = open ? 1 : 0;
+        }
+        const uint64_t b = __ballot(open);
+        if (lane == 0) wave_n[wave] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (uint32_t w = 0; w < kBlindBlock / 64; ++w) {
+            const uint32_t c = wave_n[w];
+            before += w < wave ? c : 0u;
+            all += c;
+        }
+        if (open) {
+            r.list[total + before + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = f;
+            if (r.rounds) r.rounds[f] += 1;
+        }
+        total += all;
+        __syncthreads();
+    }
+    if (tid == 0) *r.count = total;
 }
 
 // frames[f * n + i] from the embedding map (qkd_adapt::d_emb)
@@ -74,8 +156,28 @@ hipError_t launch_adapt_classes(const int32_t* src, const uint8_t* payload, uint
     return hipSuccess;
 }
 
+hipError_t launch_blind_classes(const int32_t* src, const int32_t* rank, const uint8_t* payload, const BlindArgs& b,
+                                uint32_t n, uint32_t n_payload, uint32_t n_frames, uint8_t* cls, hipStream_t stream) {
+    for (size_t f0 = 0; f0 < n_frames; f0 += kAdaptFramesPerLaunch) {
+        const size_t nf = std::min(kAdaptFramesPerLaunch, (size_t)n_frames - f0);
+        hipLaunchKernelGGL(blind_class_kernel, dim3((n + kAdaptBlock - 1) / kAdaptBlock, (unsigned)nf),
+                           dim3(kAdaptBlock), 0, stream, src, rank, payload, b.revealed, b.n_revealed, b.list, b.count,
+                           (uint32_t)f0, n, n_payload, b.p, cls);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_blind_round(const BlindRound& r, hipStream_t stream) {
+    hipLaunchKernelGGL(blind_round_kernel, dim3(1), dim3(kBlindBlock), 0, stream, r);
+    return hipGetLastError();
+}
+
 static void adapt_free(qkd_adapt* a) {
     DeviceGuard g(a->device);
+    if (a->d_rank_orig) (void)hipFree(a->d_rank_orig);
+    if (a->d_rank_int) (void)hipFree(a->d_rank_int);
     if (a->d_src_orig) (void)hipFree(a->d_src_orig);
     if (a->d_src_int) (void)hipFree(a->d_src_int);
     if (a->d_emb) (void)hipFree(a->d_emb);
@@ -97,7 +199,8 @@ static qkd_status adapt_build(qkd_adapt* a, const qkd_code* c, const int32_t* pu
         if (emb[pos] != 0) return set_error(QKD_ERR_INVALID_ARG, "qkd_adapt_create: position %d given twice", pos);
         emb[pos] = r < p ? -2 - r : -1;
     }
-    std::vector<int32_t> src(n), src_int(n), perm(n);
+    std::vector<int32_t> src(n), src_int(n), perm(n), rank(n, -1), rank_int(n);
+    for (int32_t r = 0; r < p; ++r) rank[punctured[r]] = r;
     int32_t k = 0;
     for (int32_t i = 0; i < n; ++i) {
         if (emb[i] == 0) emb[i] = k++;
@@ -114,8 +217,13 @@ static qkd_status adapt_build(qkd_adapt* a, const qkd_code* c, const int32_t* pu
     for (int32_t q = 0; q < n; ++q) {
         if (perm[q] < 0 || perm[q] >= n) return set_error(QKD_ERR_BAD_CODE, "qkd_adapt_create: bad bit order");
         src_int[q] = src[perm[q]];
+        rank_int[q] = rank[perm[q]];
     }
     const size_t bytes = (size_t)n * sizeof(int32_t);
+    QKD_HIP(hipMalloc(&a->d_rank_orig, bytes));
+    QKD_HIP(hipMalloc(&a->d_rank_int, bytes));
+    QKD_HIP(hipMemcpy(a->d_rank_orig, rank.data(), bytes, hipMemcpyHostToDevice));
+    QKD_HIP(hipMemcpy(a->d_rank_int, rank_int.data(), bytes, hipMemcpyHostToDevice));
     QKD_HIP(hipMalloc(&a->d_src_orig, bytes));
     QKD_HIP(hipMalloc(&a->d_src_int, bytes));
     QKD_HIP(hipMalloc(&a->d_emb, bytes));

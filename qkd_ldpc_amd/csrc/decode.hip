@@ -346,7 +346,11 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
     for (;;) {
         pc.mark(4);
         if (tid == 0) {
-            ctl[0] = atomicAdd(a.counter, 1u);
+            // the next frame of the queue: frame k, or with a frame list its
+            // k-th entry (past the list: no frame)
+            uint32_t k = atomicAdd(a.counter, 1u);
+            if (a.frame_list != nullptr) k = k < *a.frame_count ? a.frame_list[k] : a.n_frames;
+            ctl[0] = k;
             if (MODE == kModeClass) ctl[1] = 0;      // the frame's payload flips
         }
         for (int w = tid; w < m_words; w += kDecodeBlock) xsyn[w] = 0;
@@ -1539,6 +1543,8 @@ static qkd_status ws_free(qkd_workspace* ws) {
     if (ws->ilv) (void)hipFree(ws->ilv);
     if (ws->fb_list) (void)hipFree(ws->fb_list);
     if (ws->cls) (void)hipFree(ws->cls);
+    if (ws->blind_list) (void)hipFree(ws->blind_list);
+    if (ws->blind_open) (void)hipFree(ws->blind_open);
     if (ws->spec_stat_ev) (void)hipEventSynchronize(ws->spec_stat_ev);
     if (ws->spec_stat_host) (void)hipHostFree(ws->spec_stat_host);
     if (ws->spec_stat_ev) (void)hipEventDestroy(ws->spec_stat_ev);
@@ -1565,10 +1571,19 @@ struct WsSession {
     qkd_workspace* ws;
     hipStream_t stream;
     std::unique_lock<std::mutex> lk;
+    // a stream under capture: the workspace's event stays out of the graph (it
+    // would tie later, uncaptured calls to the capture); the caller orders the
+    // graph's replays against other users of the workspace
+    bool capturing = false;
     WsSession(qkd_workspace* w, hipStream_t s) : ws(w), stream(s), lk(w->mu) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &cs) == hipSuccess) capturing = cs != hipStreamCaptureStatusNone;
+        else (void)hipGetLastError();
+        if (capturing) return;
         if (ws->done) (void)hipStreamWaitEvent(stream, ws->done, 0);
     }
     ~WsSession() {
+        if (capturing) return;
         if (!ws->done) (void)hipEventCreateWithFlags(&ws->done, hipEventDisableTiming);
         if (ws->done) (void)hipEventRecord(ws->done, stream);
     }
@@ -1741,6 +1756,11 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
         if (mode != kModeClass) return hipSuccess;
         a.src = internal ? adapt->src_int : adapt->src_orig;
         a.cls = adapt->cls;
+        // (a round of qkd_reconcile_blind_batch: the frames of its list only)
+        if (adapt->blind)
+            return launch_blind_classes(a.src, internal ? adapt->blind->rank_int : adapt->blind->rank_orig,
+                                        adapt->bob_payload, *adapt->blind, (uint32_t)c->n, a.n_payload, a.n_frames,
+                                        adapt->cls, stream);
         return launch_adapt_classes(a.src, adapt->bob_payload, (uint32_t)c->n, a.n_payload, a.n_frames, adapt->cls,
                                     stream);
     };
@@ -2399,6 +2419,45 @@ qkd_status qkd_reconcile_batch(const qkd_code* c, qkd_workspace* ws, const uint8
                          iterations, syndromes_match, corrected, nullptr, stream);
 }
 
+// one class byte per bit and frame: the only per-bit input the class-mode decoder reads
+static qkd_status ws_reserve_classes(qkd_workspace* ws, size_t n_frames) {
+    const size_t need = n_frames * (size_t)ws->code->n;
+    if (ws->cls_bytes >= need) return QKD_OK;
+    if (ws->cls) QKD_HIP(hipFree(ws->cls));
+    ws->cls = nullptr;
+    ws->cls_bytes = 0;
+    if (hipMalloc(&ws->cls, need) != hipSuccess)
+        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of class bytes", need);
+    ws->cls_bytes = need;
+    return QKD_OK;
+}
+
+// the class-mode launch arguments of qkd_reconcile_adaptive_batch and of a
+// round of qkd_reconcile_blind_batch
+static DecodeArgs class_decode_args(const qkd_adapt* ad, const uint8_t* syndrome, size_t n_frames, double qber,
+                                    double known_llr, uint32_t max_iterations, double msg_threshold, uint32_t flags,
+                                    uint8_t* payload_out, uint8_t* frames_out, uint32_t* iterations,
+                                    uint8_t* syndromes_match, uint32_t* corrected) {
+    DecodeArgs a{};
+    a.pinf = std::numeric_limits<float>::infinity();
+    a.n_frames = (uint32_t)n_frames;
+    a.max_it = max_iterations;
+    a.thr = msg_threshold;
+    a.clamp_on = (flags & QKD_FLAG_THRESHOLD) ? 1 : 0;
+    a.log_p = std::log((1. - qber) / qber);    // as qkd_reconcile_batch (decode_keys)
+    a.known = known_llr;
+    a.syn = syndrome;
+    a.bits_out = frames_out;
+    a.payload_out = payload_out;
+    a.n_payload = (uint32_t)ad->n_payload;
+    a.flips = corrected;
+    a.iters = iterations;
+    a.sp_ok = syndromes_match;
+    a.thr_dn = f32_bound(msg_threshold, false);
+    a.thr_up = f32_bound(msg_threshold, true);
+    return a;
+}
+
 qkd_status qkd_reconcile_adaptive_batch(const qkd_code* c, qkd_workspace* ws, const qkd_adapt* ad,
                                         const uint8_t* bob_payload, const uint8_t* syndrome, size_t n_frames,
                                         double qber, double known_llr, uint32_t max_iterations,
@@ -2422,36 +2481,80 @@ qkd_status qkd_reconcile_adaptive_batch(const qkd_code* c, qkd_workspace* ws, co
     ws = resolve_ws(c, ws);
     if (!ws) return set_error(QKD_ERR_OUT_OF_MEMORY, "no workspace");
     WsSession sess(ws, (hipStream_t)stream);
-    // one class byte per bit and frame: the only per-bit input the decoder reads
-    const size_t need = n_frames * (size_t)c->n;
-    if (ws->cls_bytes < need) {
-        if (ws->cls) QKD_HIP(hipFree(ws->cls));
-        ws->cls = nullptr;
-        ws->cls_bytes = 0;
-        if (hipMalloc(&ws->cls, need) != hipSuccess)
-            return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of class bytes", need);
-        ws->cls_bytes = need;
-    }
-    DecodeArgs a{};
-    a.pinf = std::numeric_limits<float>::infinity();
-    a.n_frames = (uint32_t)n_frames;
-    a.max_it = max_iterations;
-    a.thr = msg_threshold;
-    a.clamp_on = (flags & QKD_FLAG_THRESHOLD) ? 1 : 0;
-    a.log_p = std::log((1. - qber) / qber);    // as qkd_reconcile_batch (decode_keys)
-    a.known = known_llr;
-    a.syn = syndrome;
-    a.bits_out = frames_out;
-    a.payload_out = payload_out;
-    a.n_payload = (uint32_t)ad->n_payload;
-    a.flips = corrected;
-    a.iters = iterations;
-    a.sp_ok = syndromes_match;
-    a.thr_dn = f32_bound(msg_threshold, false);
-    a.thr_up = f32_bound(msg_threshold, true);
+    s = ws_reserve_classes(ws, n_frames);
+    if (s != QKD_OK) return s;
+    DecodeArgs a = class_decode_args(ad, syndrome, n_frames, qber, known_llr, max_iterations, msg_threshold, flags,
+                                     payload_out, frames_out, iterations, syndromes_match, corrected);
     const ClassArgs ca{ad->d_src_orig, ad->d_src_int, bob_payload, ws->cls};
     return launch_decode(c, ws, a, kModeClass, flags & ~QKD_FLAG_ERASURES, (hipStream_t)stream, nullptr, nullptr,
                          &ca);
+}
+
+qkd_status qkd_reconcile_blind_batch(const qkd_code* c, qkd_workspace* ws, const qkd_adapt* ad,
+                                     const uint8_t* bob_payload, const uint8_t* syndrome, size_t n_frames,
+                                     double qber, double known_llr, uint32_t max_iterations, double msg_threshold,
+                                     uint32_t flags, const uint8_t* revealed, uint32_t* n_revealed,
+                                     const uint8_t* skip, uint32_t step, uint32_t max_rounds, uint8_t* payload_out,
+                                     uint8_t* frames_out, uint32_t* iterations, uint8_t* syndromes_match,
+                                     uint32_t* corrected, uint32_t* rounds, void* stream) {
+    clear_error();
+    if (const char* bad = qkda::reconcile_args_error(c, bob_payload, syndrome, n_frames, qber, payload_out,
+                                                     iterations, syndromes_match))
+        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    if (const char* bad = qkda::reconcile_blind_args_error(ad, n_revealed, step, max_rounds))
+        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    if (ad->code != c) return set_error(QKD_ERR_INVALID_ARG, "the plan was created for another code");
+    if (const char* bad = qkda::reconcile_blind_revealed_error(ad->p, revealed))
+        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    if (!(known_llr > 0.0) || !std::isfinite(known_llr))
+        return set_error(QKD_ERR_INVALID_ARG, "known_llr must be finite and > 0");
+    qkd_status s = check_decode_params(max_iterations, msg_threshold, flags & ~QKD_FLAG_ERASURES);
+    if (s != QKD_OK) return s;
+    if ((flags & QKD_VARIANT_MASK) != QKD_VARIANT_SP_F64)
+        return set_error(QKD_ERR_UNSUPPORTED, "qkd_reconcile_blind_batch: QKD_VARIANT_SP_F64 only");
+    DeviceGuard g(c->device);
+    ws = resolve_ws(c, ws);
+    if (!ws) return set_error(QKD_ERR_OUT_OF_MEMORY, "no workspace");
+    WsSession sess(ws, (hipStream_t)stream);
+    s = ws_reserve_classes(ws, n_frames);
+    if (s != QKD_OK) return s;
+    s = ws_reserve_decode(ws, 0);             // (the counter words)
+    if (s != QKD_OK) return s;
+    if (ws->blind_frames < n_frames) {
+        if (ws->blind_list) QKD_HIP(hipFree(ws->blind_list));
+        if (ws->blind_open) QKD_HIP(hipFree(ws->blind_open));
+        ws->blind_list = nullptr;
+        ws->blind_open = nullptr;
+        ws->blind_frames = 0;
+        if (hipMalloc(&ws->blind_list, n_frames * sizeof(uint32_t)) != hipSuccess ||
+            hipMalloc(&ws->blind_open, n_frames) != hipSuccess)
+            return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the open-frame list");
+        ws->blind_frames = n_frames;
+    }
+    // counter word 4: the round's open frames ([0..3]: the decoders' queues)
+    uint32_t* const count = ws->counter + 4;
+    const BlindArgs ba{ad->d_rank_orig, ad->d_rank_int, revealed, n_revealed, (uint32_t)ad->p, ws->blind_list, count};
+    ClassArgs ca{ad->d_src_orig, ad->d_src_int, bob_payload, ws->cls};
+    ca.blind = &ba;
+    // every round: settle the round before and list the open frames, then
+    // their class bytes and the decoder over the list (launch_decode), all on
+    // the stream; the host never learns how many frames a round has
+    // (a frame is decoded at most 1 + ceil(p / step) times: later rounds would find no open frame)
+    const uint64_t useful = step ? 1 + ((uint64_t)ad->p + step - 1) / step : 1;
+    const uint32_t n_rounds = (uint32_t)std::min<uint64_t>(max_rounds, useful);
+    for (uint32_t t = 0; t < n_rounds; ++t) {
+        const BlindRound br{t, (uint32_t)n_frames, (uint32_t)ad->p, step, skip, syndromes_match, n_revealed, rounds,
+                            ws->blind_open, ws->blind_list, count};
+        QKD_HIP(launch_blind_round(br, (hipStream_t)stream));
+        DecodeArgs a = class_decode_args(ad, syndrome, n_frames, qber, known_llr, max_iterations, msg_threshold,
+                                         flags, payload_out, frames_out, iterations, syndromes_match, corrected);
+        a.frame_list = ws->blind_list;
+        a.frame_count = count;
+        s = launch_decode(c, ws, a, kModeClass, flags & ~QKD_FLAG_ERASURES, (hipStream_t)stream, nullptr, nullptr,
+                          &ca);
+        if (s != QKD_OK) return s;
+    }
+    return QKD_OK;
 }
 
 static VerifyArgs verify_args(const qkd_code* c, uint64_t hash_seed, const uint64_t* hash_words, uint32_t tag_bits,

@@ -1,7 +1,7 @@
 // qkd_args.h — host-only argument checks of the batched entry points, free of
 // HIP so that a stand-alone host program can exercise them
 // (tests/native/reconcile_args_check.cpp, tests/native/verify_hash_check.cpp,
-// tests/native/privacy_hash_check.cpp).
+// tests/native/privacy_hash_check.cpp, tests/native/blind_args_check.cpp).
 #pragma once
 
 #include <stddef.h>
@@ -23,6 +23,25 @@ inline const char* reconcile_args_error(const void* code, const uint8_t* bob, co
     if (n_frames == 0) return "n_frames must be > 0";
     if (n_frames > 0xffffffffull) return "n_frames too large";
     if (!(qber > 0.0 && qber < 1.0)) return "QBER must be in (0,1)";
+    return nullptr;
+}
+
+// What qkd_reconcile_blind_batch adds to qkd_reconcile_adaptive_batch's
+// arguments (checked after reconcile_args_error, before the plan is looked
+// at): the plan and the reveal counts, at least one round, and a step
+// whenever a second round can follow.
+inline const char* reconcile_blind_args_error(const void* adapt, const uint32_t* n_revealed, uint32_t step,
+                                              uint32_t max_rounds) {
+    if (!adapt || !n_revealed) return "null argument";
+    if (max_rounds < 1) return "max_rounds must be >= 1";
+    if (max_rounds > 1 && step < 1) return "step must be >= 1 when max_rounds > 1";
+    return nullptr;
+}
+
+// ... and, once the plan's punctured count p is known: the revealed bytes
+// exist exactly when there is a punctured bit to reveal.
+inline const char* reconcile_blind_revealed_error(int32_t p, const uint8_t* revealed) {
+    if ((p > 0) != (revealed != nullptr)) return "revealed is required exactly when the plan punctures";
     return nullptr;
 }
 

@@ -44,7 +44,9 @@ enum DecodeMode : int {
     // qkd_reconcile_adaptive_batch: one class byte per bit (DecodeArgs::cls, in
     // the launched kernel's bit order) and the caller's syndrome bytes; the LLR
     // of a bit is the level of its class: 0 +log_p, 1 -log_p, 2 +0.0
-    // (punctured), 3 +known (shortened). Always with the erasure rule.
+    // (punctured), 3 +known (shortened), 4 +known / 5 -known (a punctured bit
+    // whose value Alice revealed: qkd_reconcile_blind_batch). Always with the
+    // erasure rule.
     kModeClass = 2
 };
 
@@ -205,8 +207,10 @@ struct DecodeArgs {
     size_t ilv_stride;
     uint32_t* fb_list;
     uint32_t* fb_count;
-    // decode_split_kernel: decode only frame_list[0 .. *frame_count) (the
-    // interleaved decoder's hand-offs), or every frame when nullptr
+    // decode_split_kernel and decode_kernel: decode only
+    // frame_list[0 .. *frame_count) (the interleaved decoder's hand-offs; the
+    // open frames of a round of qkd_reconcile_blind_batch), or every frame
+    // when nullptr
     const uint32_t* frame_list;
     const uint32_t* frame_count;
     // kModeClass: the frames' class bytes (F x N, the launched view's bit
@@ -226,7 +230,10 @@ struct DecodeArgs {
 __device__ __forceinline__ double class_llr(uint32_t cl, double log_p, double known) {
     const double a = (cl & 1u) ? -log_p : log_p;
     const double b = (cl & 1u) ? known : 0.0;
-    return (cl & 2u) ? b : a;
+    const double v = (cl & 2u) ? b : a;
+    // classes 4 and 5 (revealed bits): +known / -known
+    const double r = (cl & 1u) ? -known : known;
+    return (cl & 4u) ? r : v;
 }
 
 // The frame-interleaved decoder (decode_ilv.hip): kIlvCols frames per
@@ -791,14 +798,47 @@ hipError_t launch_verify_tags(const uint8_t* bits, uint32_t n, uint32_t n_frames
 // bytes), and the kernel that writes the class bytes of F frames from a map:
 // cls[f * n + i] = src[i] >= 0 ? payload[f * n_payload + src[i]] & 1
 //                              : src[i] == kSrcPunctured ? 2 : 3
+// qkd_reconcile_blind_batch (blind != nullptr): the class bytes of the frames
+// of the round's list only, a punctured position of rank j (rank_orig /
+// rank_int: its index in the plan's punctured list, -1 elsewhere) being
+// 4 | (revealed[f * p + j] & 1) when j < min(n_revealed[f], p), else 2.
+struct BlindArgs {
+    const int32_t* rank_orig;
+    const int32_t* rank_int;
+    const uint8_t* revealed;         // F x p (nullptr when p = 0)
+    const uint32_t* n_revealed;      // F
+    uint32_t p;
+    const uint32_t* list;            // the round's open frames
+    const uint32_t* count;           // how many of them
+};
 struct ClassArgs {
     const int32_t* src_orig;
     const int32_t* src_int;
     const uint8_t* bob_payload;
     uint8_t* cls;
+    const BlindArgs* blind = nullptr;
 };
 constexpr int32_t kSrcPunctured = -1, kSrcShortened = -2;
 hipError_t launch_adapt_classes(const int32_t* src, const uint8_t* payload, uint32_t n, uint32_t n_payload,
                                 uint32_t n_frames, uint8_t* cls, hipStream_t stream);
+// the same for the frames list[0 .. *count) only (grid sized for n_frames: a
+// block past the count exits)
+hipError_t launch_blind_classes(const int32_t* src, const int32_t* rank, const uint8_t* payload, const BlindArgs& b,
+                                uint32_t n, uint32_t n_payload, uint32_t n_frames, uint8_t* cls, hipStream_t stream);
+// One round's bookkeeping of qkd_reconcile_blind_batch (adapt.hip
+// blind_round_kernel): closes and advances the frames of the round before,
+// then compacts the open frames into list / *count in ascending order.
+struct BlindRound {
+    uint32_t round;                  // t
+    uint32_t n_frames, p, step;
+    const uint8_t* skip;             // F or nullptr
+    const uint8_t* sp_ok;            // F: the decoder's syndromes_match
+    uint32_t* n_revealed;            // F, in/out
+    uint32_t* rounds;                // F or nullptr
+    uint8_t* open;                   // F: workspace
+    uint32_t* list;
+    uint32_t* count;
+};
+hipError_t launch_blind_round(const BlindRound& r, hipStream_t stream);
 
 }  // namespace qkd

@@ -202,6 +202,11 @@ struct qkd_workspace {
     // qkd_reconcile_adaptive_batch: one class byte per bit and frame (adapt.hip)
     uint8_t* cls = nullptr;
     size_t cls_bytes = 0;
+    // qkd_reconcile_blind_batch: the open frames of a round (their count is
+    // counter word 4) and one open flag per frame
+    uint32_t* blind_list = nullptr;
+    uint8_t* blind_open = nullptr;
+    size_t blind_frames = 0;
     // qkd_debug_decoder_timing: while on, HIP events bracket every decoder
     // launch on its stream (pairs recorded, read back on collection)
     bool time_decoder = false;
@@ -305,6 +310,9 @@ struct qkd_code {
 //   d_emb[i]       embedding: the payload index k >= 0, -1 for a shortened bit,
 //                  -2 - r for the punctured bit that takes fill byte r (the
 //                  r-th of the caller's punctured list)
+//   d_rank_orig[i] that rank r for a punctured original bit i, -1 elsewhere
+//   d_rank_int[q]  the same for the internal bit q (qkd_reconcile_blind_batch
+//                  reveals the punctured bits in the order of their ranks)
 struct qkd_adapt {
     const qkd_code* code = nullptr;
     int device = 0;
@@ -312,6 +320,8 @@ struct qkd_adapt {
     int32_t* d_src_orig = nullptr;
     int32_t* d_src_int = nullptr;
     int32_t* d_emb = nullptr;
+    int32_t* d_rank_orig = nullptr;
+    int32_t* d_rank_int = nullptr;
 };
 
 namespace qkd {
