@@ -435,6 +435,71 @@ QKD_API qkd_status qkd_reconcile_blind_batch(const qkd_code *code, qkd_workspace
                                              uint32_t *iterations, uint8_t *syndromes_match, uint32_t *corrected,
                                              uint32_t *rounds, void *stream);
 
+/* ---- key verification of punctured and shortened frames ----------------------
+ * The verification hash above applied to the payload: positions are payload
+ * indices k, 0 <= k < n_payload, the key string has
+ * W = qkd_verify_key_words(n_payload) words (hash_words[W] on the device, or
+ * expanded from hash_seed when hash_words is NULL), tag_bits is 1..64 and a key
+ * bit is byte & 1. With the same string the tag is the low tag_bits bits of
+ * qkd_privacy_amplify_batch(n_in = n_payload, out_bits = 64) on the payload.
+ *
+ * Alice's half: tags[f] = tag(payload[f]) for payload[F * n_payload] on the
+ * plan's device. One launch of the byte-key tag kernel on the stream, no
+ * workspace, no host copy, no synchronisation: capturable. Validated as
+ * qkd_verify_tags_batch, with the plan in the code's place. */
+QKD_API qkd_status qkd_adapt_verify_tags_batch(const qkd_adapt *adapt, const uint8_t *payload, size_t n_frames,
+                                               uint64_t hash_seed, const uint64_t *hash_words, uint32_t tag_bits,
+                                               uint64_t *tags, void *stream);
+
+/* Bob's half on the rate-adaptive path: qkd_reconcile_adaptive_batch (same
+ * arguments, same order, and bit for bit the same payload_out, frames_out,
+ * iterations, syndromes_match and corrected) with the payload's tag taken by
+ * the decoder kernel itself, in the loop that writes payload_out: no separate
+ * pass over the payload. hash_seed .. verified mean what they mean for
+ * qkd_reconcile_verify_batch and follow its rules (at least one of alice_tags
+ * and tags_out; verified exactly when alice_tags is given; QKD_ERR_INVALID_ARG
+ * before any device work otherwise):
+ *   tags_out[f] = tag(payload_out[f]), masked, whether or not the frame matched;
+ *   verified[f] = syndromes_match[f] && ((tag ^ alice_tags[f]) & mask) == 0.
+ * The seeded key string is expanded once per call by a small kernel into the
+ * workspace (grow-on-demand). */
+QKD_API qkd_status qkd_reconcile_adaptive_verify_batch(
+    const qkd_code *code, qkd_workspace *ws, const qkd_adapt *adapt, const uint8_t *bob_payload,
+    const uint8_t *syndrome, size_t n_frames, double qber, double known_llr, uint32_t max_iterations,
+    double msg_threshold, uint32_t flags, uint8_t *payload_out, uint8_t *frames_out, uint32_t *iterations,
+    uint8_t *syndromes_match, uint32_t *corrected, uint64_t hash_seed, const uint64_t *hash_words,
+    uint32_t tag_bits, const uint64_t *alice_tags, uint64_t *tags_out, uint8_t *verified, void *stream);
+
+/* Bob's half of blind reconciliation with verification:
+ * qkd_reconcile_blind_batch's arguments followed by the same six. Alice
+ * announces one tag per frame together with the syndrome; Bob compares in every
+ * round; the disclosure is tag_bits once per frame.
+ *  - With alice_tags given, every clause of qkd_reconcile_blind_batch's contract
+ *    that reads "a frame that matched" reads "a frame that is verified": a frame
+ *    is closed when verified[f] holds. A frame whose syndrome matches but whose
+ *    tag differs is treated exactly like a failed frame: closed if
+ *    n_revealed[f] >= p, otherwise, while another round follows, given `step`
+ *    more bits and decoded again (a revealed bit that contradicts the wrong word
+ *    can move the decoder off it; Alice sends nothing new for this).
+ *  - With only tags_out given, closing stays on syndromes_match.
+ *  - tags_out and verified are overwritten with each round's values like the
+ *    other outputs, and are not written for skipped frames.
+ *  - max_rounds = 1 stays Bob's step on a real link; he sets skip from verified.
+ *  - If every frame whose syndrome matches also has a matching tag, all other
+ *    outputs equal qkd_reconcile_blind_batch's.
+ * The kernel-and-launch contract of qkd_reconcile_blind_batch holds unchanged
+ * (the round kernel reads verified in place of syndromes_match): no host
+ * synchronisation, no host copy, no allocation beyond the workspace's
+ * grow-on-demand; capturable once the workspace has its size. */
+QKD_API qkd_status qkd_reconcile_blind_verify_batch(
+    const qkd_code *code, qkd_workspace *ws, const qkd_adapt *adapt, const uint8_t *bob_payload,
+    const uint8_t *syndrome, size_t n_frames, double qber, double known_llr, uint32_t max_iterations,
+    double msg_threshold, uint32_t flags, const uint8_t *revealed, uint32_t *n_revealed, const uint8_t *skip,
+    uint32_t step, uint32_t max_rounds, uint8_t *payload_out, uint8_t *frames_out, uint32_t *iterations,
+    uint8_t *syndromes_match, uint32_t *corrected, uint32_t *rounds, uint64_t hash_seed,
+    const uint64_t *hash_words, uint32_t tag_bits, const uint64_t *alice_tags, uint64_t *tags_out,
+    uint8_t *verified, void *stream);
+
 /* ---- privacy amplification --------------------------------------------------
  * The last step before a secret key: the corrected (and verified) key is
  * hashed down to out_bits bits with a matrix of the same Hankel family as the

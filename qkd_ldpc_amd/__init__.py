@@ -451,26 +451,38 @@ def _need_tags(t, count: int, name: str, H: HMatrix):
     _need_vec(t, t.dtype, count, name, H)
 
 
-def _verify_key(H: HMatrix, hash_seed, hash_words):
-    """(seed, words) of the hash's key string: the caller's device words, or the seed."""
+def _verify_width(H) -> int:
+    """The key width the verification hash runs over: N of an HMatrix, n_payload of an
+    AdaptPlan."""
+    return H.n_payload if hasattr(H, "n_payload") else H.num_bit_nodes
+
+
+def _verify_key(H, hash_seed, hash_words):
+    """(seed, words) of the hash's key string: the caller's device words, or the seed.
+    H: an HMatrix, or an AdaptPlan (the string is then sized from n_payload)."""
     if hash_words is not None:
-        _need_tags(hash_words, verify_key_words(H.num_bit_nodes), "hash_words", H)
+        _need_tags(hash_words, verify_key_words(_verify_width(H)), "hash_words", H)
     return (0 if hash_seed is None else int(hash_seed)) & (2**64 - 1), hash_words
 
 
-def verify_tags(H: HMatrix, bits, hash_seed: int = 0, hash_words=None, tag_bits: int = 64, stream=None):
+def verify_tags(H, bits, hash_seed: int = 0, hash_words=None, tag_bits: int = 64, stream=None):
     """Key verification tags of byte keys (qkd_verify_tags_batch), Alice's half of the
     check that follows error correction: tags[f] = the Hankel-matrix universal hash of
     bits[f] ([F, N] uint8, a key bit is byte & 1), low tag_bits bits, as int64 bit
     patterns. The key string is hash_words (verify_key_words(N) 64-bit words on the
     device, truly random: the 2^-tag_bits universal form) or, without them, expanded from
-    hash_seed (a computational stand-in). A tag discloses tag_bits bits of the key."""
+    hash_seed (a computational stand-in). A tag discloses tag_bits bits of the key.
+
+    With an AdaptPlan in H's place (qkd_adapt_verify_tags_batch): the tags of payloads
+    [F, n_payload], positions being payload indices and N above n_payload; what
+    reconcile_adaptive and reconcile_blind compare with as alice_tags."""
+    width = _verify_width(H)
     _need_cuda(bits, torch.uint8, "bits", H)
-    f = _frames(bits, H.num_bit_nodes, "bits")
+    f = _frames(bits, width, "bits")
     seed, words = _verify_key(H, hash_seed, hash_words)
     tags = torch.empty(f, dtype=torch.int64, device=bits.device)
-    N.check(N.lib().qkd_verify_tags_batch(H.handle, _ptr(bits), f, seed, _ptr(words), tag_bits, _ptr(tags),
-                                          _stream(stream, H.device)))
+    entry = N.lib().qkd_adapt_verify_tags_batch if hasattr(H, "n_payload") else N.lib().qkd_verify_tags_batch
+    N.check(entry(H.handle, _ptr(bits), f, seed, _ptr(words), tag_bits, _ptr(tags), _stream(stream, H.device)))
     return tags
 
 
@@ -582,14 +594,23 @@ def adapt_extract(plan: AdaptPlan, frames, stream=None):
 def reconcile_adaptive(H: HMatrix, plan: AdaptPlan, bob_payload, syndrome, qber: float,
                        known_llr: float = 100.0, max_iterations: int = 50, msg_threshold: float = 100.0,
                        threshold_enabled: bool = True, want_corrected: bool = True,
-                       want_frames: bool = False, workspace=None, stream=None) -> ReconcileResult:
+                       want_frames: bool = False, workspace=None, stream=None,
+                       hash_seed: int | None = None, hash_words=None, tag_bits: int = 64, alice_tags=None,
+                       want_tags: bool = False) -> ReconcileResult:
     """Bob's side with punctured and shortened frames (qkd_reconcile_adaptive_batch):
     bob_payload [F, n_payload] uint8, syndrome [F, M] uint8 of Alice's embedded frames. The
     decision equals sum_product_decoding(erasures=True) on the LLRs +-log((1-q)/q) at the
     payload positions, +0.0 at the punctured and +known_llr at the shortened ones, without
     that array ever existing. bits: the payload of the decision; corrected:
     popcount(bits ^ bob_payload); frames (want_frames): the whole N-bit decisions. The
-    default known_llr is the default clamp, so a shortened bit publishes t = 1.0 exactly."""
+    default known_llr is the default clamp, so a shortened bit publishes t = 1.0 exactly.
+
+    Key verification (qkd_reconcile_adaptive_verify_batch), with any of hash_seed,
+    hash_words, alice_tags, want_tags given, exactly as on reconcile: tags =
+    verify_tags(plan, bits), taken by the decoder kernel as it writes the payload; with
+    alice_tags [F] (Alice's verify_tags(plan, payload) under the same hash), verified =
+    syndromes_match & (tag == alice_tags) over the low tag_bits bits. Every other field is
+    what the call without them returns."""
     _need_cuda(bob_payload, torch.uint8, "bob_payload", H)
     _need_cuda(syndrome, torch.uint8, "syndrome", H)
     f = _frames(bob_payload, plan.n_payload, "bob_payload")
@@ -601,6 +622,17 @@ def reconcile_adaptive(H: HMatrix, plan: AdaptPlan, bob_payload, syndrome, qber:
     ok = torch.empty(f, dtype=torch.uint8, device=dev)
     corrected = torch.empty(f, dtype=torch.int32, device=dev) if want_corrected else None
     flags = decoder_flags(threshold_enabled, "sp_f64")
+    if hash_seed is not None or hash_words is not None or alice_tags is not None or want_tags:
+        seed, words = _verify_key(plan, hash_seed, hash_words)
+        if alice_tags is not None:
+            _need_tags(alice_tags, f, "alice_tags", H)
+        tags = torch.empty(f, dtype=torch.int64, device=dev)
+        verified = torch.empty(f, dtype=torch.uint8, device=dev) if alice_tags is not None else None
+        N.check(N.lib().qkd_reconcile_adaptive_verify_batch(
+            H.handle, _ws(workspace), plan.handle, _ptr(bob_payload), _ptr(syndrome), f, qber, known_llr,
+            max_iterations, msg_threshold, flags, _ptr(bits), _ptr(frames), _ptr(iters), _ptr(ok), _ptr(corrected),
+            seed, _ptr(words), tag_bits, _ptr(alice_tags), _ptr(tags), _ptr(verified), _stream(stream, H.device)))
+        return ReconcileResult(iters, ok, bits, corrected, tags, verified, frames=frames)
     N.check(N.lib().qkd_reconcile_adaptive_batch(
         H.handle, _ws(workspace), plan.handle, _ptr(bob_payload), _ptr(syndrome), f, qber, known_llr,
         max_iterations, msg_threshold, flags, _ptr(bits), _ptr(frames), _ptr(iters), _ptr(ok), _ptr(corrected),
@@ -614,7 +646,9 @@ class BlindResult(ReconcileResult):
     entries are left as allocated, never written), rounds (how many rounds decoded the
     frame), n_revealed (the revealed-bit count its last decode used) and leak_bits =
     M - p + n_revealed, the key bits the exchange disclosed for that frame, which the
-    caller takes off in privacy amplification (all int32, on the device)."""
+    caller takes off in privacy amplification (all int32, on the device). A verified link
+    (alice_tags) additionally discloses tag_bits bits per frame, once; leak_bits does not
+    include them."""
     rounds: "torch.Tensor | None" = None
     n_revealed: "torch.Tensor | None" = None
     leak_bits: "torch.Tensor | None" = None
@@ -624,7 +658,9 @@ def reconcile_blind(H: HMatrix, plan: AdaptPlan, bob_payload, syndrome, qber: fl
                     revealed=None, n_revealed=None, skip=None, step: int = 0, max_rounds: int = 1,
                     known_llr: float = 100.0, max_iterations: int = 50, msg_threshold: float = 100.0,
                     threshold_enabled: bool = True, want_corrected: bool = True,
-                    want_frames: bool = False, workspace=None, stream=None) -> BlindResult:
+                    want_frames: bool = False, workspace=None, stream=None,
+                    hash_seed: int | None = None, hash_words=None, tag_bits: int = 64, alice_tags=None,
+                    want_tags: bool = False) -> BlindResult:
     """Blind reconciliation, Bob's side (qkd_reconcile_blind_batch): reconcile_adaptive
     made interactive. revealed [F, p] uint8: the values (byte & 1) of the punctured bits in
     the order of the plan's punctured list, i.e. Alice's fill, of which frame f holds the
@@ -642,7 +678,15 @@ def reconcile_blind(H: HMatrix, plan: AdaptPlan, bob_payload, syndrome, qber: fl
     int32 count means "everything revealed" (it cannot be rejected without a
     synchronisation). With stream= given, the copy of n_revealed and leak_bits are made on
     that stream too, after whatever it already holds: the inputs must be ready there, and
-    the result is ready once that stream is."""
+    the result is ready once that stream is.
+
+    Key verification (qkd_reconcile_blind_verify_batch), with any of hash_seed, hash_words,
+    alice_tags, want_tags given, exactly as on reconcile: tags and verified of each frame's
+    last decode. With alice_tags (Alice's verify_tags(plan, payload), announced with the
+    syndrome) "matched" above reads "verified": a frame whose syndrome matches under a
+    wrong tag is treated like a failed one, revealed more bits and decoded again, and on a
+    link Bob sets skip from verified. With want_tags alone, closing stays on
+    syndromes_match."""
     _need_cuda(bob_payload, torch.uint8, "bob_payload", H)
     _need_cuda(syndrome, torch.uint8, "syndrome", H)
     f = _frames(bob_payload, plan.n_payload, "bob_payload")
@@ -671,18 +715,35 @@ def reconcile_blind(H: HMatrix, plan: AdaptPlan, bob_payload, syndrome, qber: fl
     corrected = torch.empty(f, dtype=torch.int32, device=dev) if want_corrected else None
     rounds = torch.empty(f, dtype=torch.int32, device=dev)
     flags = decoder_flags(threshold_enabled, "sp_f64")
+    verify = hash_seed is not None or hash_words is not None or alice_tags is not None or want_tags
+    tags = verified = None
+    if verify:
+        seed, words = _verify_key(plan, hash_seed, hash_words)
+        if alice_tags is not None:
+            _need_tags(alice_tags, f, "alice_tags", H)
+        tags = torch.empty(f, dtype=torch.int64, device=dev)
+        verified = torch.empty(f, dtype=torch.uint8, device=dev) if alice_tags is not None else None
     # The copy of the counts before the call and leak_bits after it are torch work of this
     # wrapper: they go on the launch stream, where the kernels that read and advance the
     # counts run, not on whatever stream is current.
     with torch.cuda.stream(_torch_stream(stream, H.device)):
         nrev = torch.zeros(f, dtype=torch.int32, device=dev) if n_revealed is None else n_revealed.clone()
-        N.check(N.lib().qkd_reconcile_blind_batch(
-            H.handle, _ws(workspace), plan.handle, _ptr(bob_payload), _ptr(syndrome), f, qber, known_llr,
-            max_iterations, msg_threshold, flags, _ptr(revealed), _ptr(nrev), _ptr(skip), step, max_rounds,
-            _ptr(bits), _ptr(frames), _ptr(iters), _ptr(ok), _ptr(corrected), _ptr(rounds),
-            _stream(stream, H.device)))
+        if verify:
+            N.check(N.lib().qkd_reconcile_blind_verify_batch(
+                H.handle, _ws(workspace), plan.handle, _ptr(bob_payload), _ptr(syndrome), f, qber, known_llr,
+                max_iterations, msg_threshold, flags, _ptr(revealed), _ptr(nrev), _ptr(skip), step, max_rounds,
+                _ptr(bits), _ptr(frames), _ptr(iters), _ptr(ok), _ptr(corrected), _ptr(rounds),
+                seed, _ptr(words), tag_bits, _ptr(alice_tags), _ptr(tags), _ptr(verified),
+                _stream(stream, H.device)))
+        else:
+            N.check(N.lib().qkd_reconcile_blind_batch(
+                H.handle, _ws(workspace), plan.handle, _ptr(bob_payload), _ptr(syndrome), f, qber, known_llr,
+                max_iterations, msg_threshold, flags, _ptr(revealed), _ptr(nrev), _ptr(skip), step, max_rounds,
+                _ptr(bits), _ptr(frames), _ptr(iters), _ptr(ok), _ptr(corrected), _ptr(rounds),
+                _stream(stream, H.device)))
         leak = nrev + (H.num_check_nodes - p)
-    return BlindResult(iters, ok, bits, corrected, frames=frames, rounds=rounds, n_revealed=nrev, leak_bits=leak)
+    return BlindResult(iters, ok, bits, corrected, tags, verified, frames=frames, rounds=rounds, n_revealed=nrev,
+                       leak_bits=leak)
 
 
 class _Device:

@@ -72,6 +72,7 @@ EXPORTS = [
     "qkd_adapt_create", "qkd_adapt_destroy", "qkd_adapt_get_info", "qkd_adapt_positions",
     "qkd_adapt_embed_batch", "qkd_adapt_extract_batch", "qkd_reconcile_adaptive_batch",
     "qkd_reconcile_blind_batch",
+    "qkd_adapt_verify_tags_batch", "qkd_reconcile_adaptive_verify_batch", "qkd_reconcile_blind_verify_batch",
 ]
 
 
@@ -150,6 +151,11 @@ def lib():
             "qkd_reconcile_adaptive_batch": (st, [P, P, P, P, P, SZ, D, D, U32, D, U32, P, P, P, P, P, P]),
             "qkd_reconcile_blind_batch": (st, [P, P, P, P, P, SZ, D, D, U32, D, U32, P, P, P, U32, U32,
                                                P, P, P, P, P, P, P]),
+            "qkd_adapt_verify_tags_batch": (st, [P, P, SZ, U64, P, U32, P, P]),
+            "qkd_reconcile_adaptive_verify_batch": (st, [P, P, P, P, P, SZ, D, D, U32, D, U32, P, P, P, P, P,
+                                                         U64, P, U32, P, P, P, P]),
+            "qkd_reconcile_blind_verify_batch": (st, [P, P, P, P, P, SZ, D, D, U32, D, U32, P, P, P, U32, U32,
+                                                      P, P, P, P, P, P, U64, P, U32, P, P, P, P]),
             "qkd_keygen_batch": (st, [P, P, P, U64, SZ, D, P, P, P, P]),
             "qkd_trials_batch": (st, [P, P, P, U64, SZ, D, U32, D, U32, P, P, P, P, P, P]),
             "qkd_counters_batch": (st, [P, P, P, SZ, P, C.c_int, P]),

@@ -69,10 +69,11 @@ __global__ __launch_bounds__(kAdaptBlock) void blind_class_kernel(const int32_t*
 // One round's bookkeeping of qkd_reconcile_blind_batch (BlindRound), one
 // workgroup. Round 0 opens every frame that is not skipped (n_revealed past p
 // counts as p, rounds = 0). A later round first settles the frames the round
-// before decoded: a frame that matched is closed, so is one that failed with
-// nothing left to reveal; any other gets step more bits, up to p. Then the
-// open frames go to list in ascending order (rounds[f] counts the rounds that
-// decode f) and *count says how many.
+// before decoded: a frame that matched (with Alice's tags given,
+// qkd_reconcile_blind_verify_batch: one that is verified) is closed, so is one
+// that failed with nothing left to reveal; any other gets step more bits, up to
+// p. Then the open frames go to list in ascending order (rounds[f] counts the
+// rounds that decode f) and *count says how many.
 constexpr int kBlindBlock = 1024;
 __global__ __launch_bounds__(kBlindBlock) void blind_round_kernel(BlindRound r) {
     __shared__ uint32_t wave_n[kBlindBlock / 64];
@@ -90,7 +91,9 @@ __global__ __launch_bounds__(kBlindBlock) void blind_round_kernel(BlindRound r) 
                 }
             } else if (r.open[f]) {
                 const uint32_t nr = r.n_revealed[f];
-                open = r.sp_ok[f] == 0 && nr < r.p;
+                // (closed: verified when Alice's tags were given, else matched)
+                const uint8_t closed = r.verified ? r.verified[f] : r.sp_ok[f];
+                open = closed == 0 && nr < r.p;
                 if (open) r.n_revealed[f] = r.step >= r.p - nr ? r.p : nr + r.step;
             }
             r.open[f] = open ? 1 : 0;
@@ -171,6 +174,20 @@ hipError_t launch_blind_classes(const int32_t* src, const int32_t* rank, const u
 
 hipError_t launch_blind_round(const BlindRound& r, hipStream_t stream) {
     hipLaunchKernelGGL(blind_round_kernel, dim3(1), dim3(kBlindBlock), 0, stream, r);
+    return hipGetLastError();
+}
+
+// The seeded key string of the verification hash, word k per thread
+// (qkd_verify.h: counter form, so no word depends on another).
+__global__ __launch_bounds__(kAdaptBlock) void verify_expand_kernel(uint64_t seed, uint32_t words,
+                                                                    uint64_t* __restrict__ out) {
+    const uint32_t k = blockIdx.x * kAdaptBlock + threadIdx.x;
+    if (k < words) out[k] = qkdv::verify_key_word(seed, k);
+}
+
+hipError_t launch_verify_expand(uint64_t seed, uint32_t words, uint64_t* out, hipStream_t stream) {
+    hipLaunchKernelGGL(verify_expand_kernel, dim3((words + kAdaptBlock - 1) / kAdaptBlock), dim3(kAdaptBlock), 0,
+                       stream, seed, words, out);
     return hipGetLastError();
 }
 

@@ -289,9 +289,14 @@ __device__ __forceinline__ void first_check_phase(const uint2* __restrict__ plan
 // ERA: the binary64 rule extended to zero LLRs (QKD_FLAG_ERASURES; edge_out);
 // kModeClass (qkd_reconcile_adaptive_batch, class bytes in the original bit
 // order) always has it.
-template <int MODE, int RULE, int DC, bool CLAMP, bool GT, bool ERA = false>
+// VFY (kModeClass): the payload's verification tag from the output loop
+// (DecodeArgs::vkey). A template parameter, not a branch on vkey: the branch
+// cost every class-mode instantiation SGPR spills and a VGPR, and the DC = 64
+// ones scratch (profiles/adapt_verify_kernel_resources.txt).
+template <int MODE, int RULE, int DC, bool CLAMP, bool GT, bool ERA = false, bool VFY = false>
 __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
     using T = typename RuleMsg<RULE>::T;
+    static_assert(!VFY || MODE == kModeClass, "payload tags: the class-byte mode");
     static_assert(!ERA || RULE == kRuleSp64, "erasure rule: binary64");
     static_assert(MODE != kModeClass || ERA, "class bytes: always with the erasure rule");
     // the exact QKD-path shortcuts (first/second-iteration tables) exist for
@@ -608,6 +613,8 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
         // ---- outputs: SP_result + last hard decision (+ keys_match)
         bool key_mismatch = false;
         uint32_t nflip = 0;
+        constexpr bool vfy = VFY;     // (kModeClass: the payload's verification tag)
+        uint64_t vacc = 0;
         for (int i = tid; i < c.n; i += kDecodeBlock) {
             const uint8_t d = total[i] <= 0 ? 1 : 0;
             if (a.bits_out) a.bits_out[(size_t)f * c.n + i] = d;
@@ -617,6 +624,7 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
                 if (k >= 0) {
                     a.payload_out[(size_t)f * a.n_payload + (uint32_t)k] = d;
                     nflip += (uint32_t)(d ^ (a.cls[(size_t)f * c.n + i] & 1u));
+                    if (vfy) vacc ^= class_verify_window(a.vkey, (uint32_t)k, d);
                 }
             }
             if (MODE == kModeKeys && !given) {
@@ -629,10 +637,18 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_kernel(DecodeArgs a) {
             const bool km = block_any(key_mismatch, ctl + 2, any_k);
             if (tid == 0 && a.key_ok) a.key_ok[f] = km ? 0 : 1;   // arrays_equal (:433)
         }
-        if (MODE == kModeClass && a.flips) {
-            if (nflip) atomicAdd(ctl + 1, nflip);
+        if (MODE == kModeClass && (a.flips || vfy)) {
+            if (a.flips && nflip) atomicAdd(ctl + 1, nflip);
+            // the waves' XORs in the tanh rows (free since the last check phase,
+            // and until the next frame's first one)
+            uint64_t* const vred = reinterpret_cast<uint64_t*>(smem + L.tval);
+            if (vfy) {
+                const uint64_t wx = wave_xor64(vacc);
+                if (lane == 0) vred[wave] = wx;
+            }
             __syncthreads();
-            if (tid == 0) a.flips[f] = ctl[1];
+            if (tid == 0 && a.flips) a.flips[f] = ctl[1];
+            if (tid == 0 && vfy) class_verify_finish(vred, a.vmask, a.vtags, a.valice, a.vok, f, done);
         }
         if (tid == 0) {
             a.iters[f] = done ? it + 1 : a.max_it;
@@ -1395,27 +1411,32 @@ static DecodeFn pick_decode_rule(int rule, bool clamp, int max_dc, int* dc) {
 
 // the erasure rule's kernels (binary64): the LLR path with QKD_FLAG_ERASURES
 // and the class-byte path
-template <int MODE, bool CLAMP, bool GT>
+template <int MODE, bool CLAMP, bool GT, bool VFY = false>
 static DecodeFn pick_decode_era_dc(int max_dc, int* dc) {
     if constexpr (!GT) {
-        if (max_dc <= 4) { *dc = 4; return decode_kernel<MODE, kRuleSp64, 4, CLAMP, false, true>; }
-        if (max_dc <= 6) { *dc = 6; return decode_kernel<MODE, kRuleSp64, 6, CLAMP, false, true>; }
-        if (max_dc <= 8) { *dc = 8; return decode_kernel<MODE, kRuleSp64, 8, CLAMP, false, true>; }
+        if (max_dc <= 4) { *dc = 4; return decode_kernel<MODE, kRuleSp64, 4, CLAMP, false, true, VFY>; }
+        if (max_dc <= 6) { *dc = 6; return decode_kernel<MODE, kRuleSp64, 6, CLAMP, false, true, VFY>; }
+        if (max_dc <= 8) { *dc = 8; return decode_kernel<MODE, kRuleSp64, 8, CLAMP, false, true, VFY>; }
     }
-    if (max_dc <= 16) { *dc = 16; return decode_kernel<MODE, kRuleSp64, 16, CLAMP, GT, true>; }
+    if (max_dc <= 16) { *dc = 16; return decode_kernel<MODE, kRuleSp64, 16, CLAMP, GT, true, VFY>; }
     *dc = 64;
-    return decode_kernel<MODE, kRuleSp64, 64, CLAMP, GT, true>;
+    return decode_kernel<MODE, kRuleSp64, 64, CLAMP, GT, true, VFY>;
 }
-template <int MODE>
+template <int MODE, bool VFY = false>
 static DecodeFn pick_decode_era(bool clamp, int max_dc, bool gt, int* dc) {
     if (gt)
-        return clamp ? pick_decode_era_dc<MODE, true, true>(max_dc, dc) : pick_decode_era_dc<MODE, false, true>(max_dc, dc);
-    return clamp ? pick_decode_era_dc<MODE, true, false>(max_dc, dc) : pick_decode_era_dc<MODE, false, false>(max_dc, dc);
+        return clamp ? pick_decode_era_dc<MODE, true, true, VFY>(max_dc, dc)
+                     : pick_decode_era_dc<MODE, false, true, VFY>(max_dc, dc);
+    return clamp ? pick_decode_era_dc<MODE, true, false, VFY>(max_dc, dc)
+                 : pick_decode_era_dc<MODE, false, false, VFY>(max_dc, dc);
 }
 
-static DecodeFn pick_decode(int mode, int rule, bool clamp, int max_dc, bool gt, int* dc, bool era = false) {
+// vfy (kModeClass): the instantiations that take the payload's tag (DecodeArgs::vkey)
+static DecodeFn pick_decode(int mode, int rule, bool clamp, int max_dc, bool gt, int* dc, bool era = false,
+                            bool vfy = false) {
     if (era || mode == kModeClass) {
         if (rule != kRuleSp64 || mode == kModeKeys) return nullptr;
+        if (mode == kModeClass && vfy) return pick_decode_era<kModeClass, true>(clamp, max_dc, gt, dc);
         return mode == kModeClass ? pick_decode_era<kModeClass>(clamp, max_dc, gt, dc)
                                   : pick_decode_era<kModeLlr>(clamp, max_dc, gt, dc);
     }
@@ -1545,6 +1566,7 @@ static qkd_status ws_free(qkd_workspace* ws) {
     if (ws->cls) (void)hipFree(ws->cls);
     if (ws->blind_list) (void)hipFree(ws->blind_list);
     if (ws->blind_open) (void)hipFree(ws->blind_open);
+    if (ws->vkey) (void)hipFree(ws->vkey);
     if (ws->spec_stat_ev) (void)hipEventSynchronize(ws->spec_stat_ev);
     if (ws->spec_stat_host) (void)hipHostFree(ws->spec_stat_host);
     if (ws->spec_stat_ev) (void)hipEventDestroy(ws->spec_stat_ev);
@@ -1807,7 +1829,8 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
         const DecodeArgs a_in = a;
         int sdc = 0;
         DecodeFn sfn = long_code ? pick_split_long(a.clamp_on != 0, c->max_dc, &sdc)
-                                 : pick_split_decode(mode, rule, a.clamp_on != 0, c->max_dc, &sdc, era);
+                                 : pick_split_decode(mode, rule, a.clamp_on != 0, c->max_dc, &sdc, era,
+                                                     mode == kModeClass && a.vkey != nullptr);
         if (!sfn) return set_error(QKD_ERR_UNSUPPORTED, "no split kernel with the erasure rule for this launch");
         const int esz = rule == kRuleSp64 ? 8 : 4;
         // diagnostic: QKD_SPLIT_BUDGET lowers the LDS budget (fewer LDS slots)
@@ -2097,7 +2120,8 @@ classic_path:
         a.first_table = 0;
         a.tab2_entries = 0;
     }
-    DecodeFn fn = pick_decode(mode, rule, a.clamp_on != 0, c->max_dc, gt, &dc, era);
+    DecodeFn fn = pick_decode(mode, rule, a.clamp_on != 0, c->max_dc, gt, &dc, era,
+                              mode == kModeClass && a.vkey != nullptr);
     if (!fn) return set_error(QKD_ERR_UNSUPPORTED, "no classic kernel with the erasure rule for this launch");
     const size_t lds = decode_lds_bytes(c, dc, a.tab2_entries, rule, gt, a.ms_sc != 0);
     int grid = 0;
@@ -2458,6 +2482,82 @@ static DecodeArgs class_decode_args(const qkd_adapt* ad, const uint8_t* syndrome
     return a;
 }
 
+// Key verification of a class-mode call (qkd_reconcile_adaptive_verify_batch,
+// qkd_reconcile_blind_verify_batch), as the caller gave it.
+struct ClassVerify {
+    uint64_t seed;
+    const uint64_t* words;
+    uint32_t tag_bits;
+    const uint64_t* alice_tags;
+    uint64_t* tags_out;
+    uint8_t* verified;
+};
+
+// The key string of a verifying class-mode call, once per call: the caller's
+// words as they are, or the seed's expansion into the workspace's buffer
+// (grow-on-demand; one small launch on the stream).
+static qkd_status class_verify_key(qkd_workspace* ws, const qkd_adapt* ad, const ClassVerify& cv, hipStream_t stream,
+                                   const uint64_t** key) {
+    if (cv.words) {
+        *key = cv.words;
+        return QKD_OK;
+    }
+    const size_t words = qkdv::verify_key_words(ad->n_payload);
+    if (ws->vkey_words < words) {
+        if (ws->vkey) QKD_HIP(hipFree(ws->vkey));
+        ws->vkey = nullptr;
+        ws->vkey_words = 0;
+        if (hipMalloc(&ws->vkey, words * sizeof(uint64_t)) != hipSuccess)
+            return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the verification key string");
+        ws->vkey_words = words;
+    }
+    QKD_HIP(launch_verify_expand(cv.seed, (uint32_t)words, ws->vkey, stream));
+    *key = ws->vkey;
+    return QKD_OK;
+}
+
+static void class_verify_into(DecodeArgs& a, const ClassVerify& cv, const uint64_t* key) {
+    a.vkey = key;
+    a.vmask = qkdv::verify_tag_mask(cv.tag_bits);
+    a.valice = cv.alice_tags;
+    a.vtags = cv.tags_out;
+    a.vok = cv.verified;
+}
+
+// qkd_reconcile_adaptive_batch and qkd_reconcile_adaptive_verify_batch after
+// their argument checks; cv: the second's tags, nullptr for the first.
+static qkd_status adaptive_run(const char* entry, const qkd_code* c, qkd_workspace* ws, const qkd_adapt* ad,
+                               const uint8_t* bob_payload, const uint8_t* syndrome, size_t n_frames, double qber,
+                               double known_llr, uint32_t max_iterations, double msg_threshold, uint32_t flags,
+                               uint8_t* payload_out, uint8_t* frames_out, uint32_t* iterations,
+                               uint8_t* syndromes_match, uint32_t* corrected, const ClassVerify* cv, void* stream) {
+    if (ad->code != c) return set_error(QKD_ERR_INVALID_ARG, "the plan was created for another code");
+    if (!(known_llr > 0.0) || !std::isfinite(known_llr))
+        return set_error(QKD_ERR_INVALID_ARG, "known_llr must be finite and > 0");
+    // QKD_FLAG_ERASURES is implied; the decode parameters as qkd_reconcile_batch
+    qkd_status s = check_decode_params(max_iterations, msg_threshold, flags & ~QKD_FLAG_ERASURES);
+    if (s != QKD_OK) return s;
+    if ((flags & QKD_VARIANT_MASK) != QKD_VARIANT_SP_F64)
+        return set_error(QKD_ERR_UNSUPPORTED, "%s: QKD_VARIANT_SP_F64 only", entry);
+    DeviceGuard g(c->device);
+    ws = resolve_ws(c, ws);
+    if (!ws) return set_error(QKD_ERR_OUT_OF_MEMORY, "no workspace");
+    WsSession sess(ws, (hipStream_t)stream);
+    s = ws_reserve_classes(ws, n_frames);
+    if (s != QKD_OK) return s;
+    DecodeArgs a = class_decode_args(ad, syndrome, n_frames, qber, known_llr, max_iterations, msg_threshold, flags,
+                                     payload_out, frames_out, iterations, syndromes_match, corrected);
+    if (cv) {
+        const uint64_t* key = nullptr;
+        s = class_verify_key(ws, ad, *cv, (hipStream_t)stream, &key);
+        if (s != QKD_OK) return s;
+        class_verify_into(a, *cv, key);
+    }
+    const ClassArgs ca{ad->d_src_orig, ad->d_src_int, bob_payload, ws->cls};
+    return launch_decode(c, ws, a, kModeClass, flags & ~QKD_FLAG_ERASURES, (hipStream_t)stream, nullptr, nullptr,
+                         &ca);
+}
+
 qkd_status qkd_reconcile_adaptive_batch(const qkd_code* c, qkd_workspace* ws, const qkd_adapt* ad,
                                         const uint8_t* bob_payload, const uint8_t* syndrome, size_t n_frames,
                                         double qber, double known_llr, uint32_t max_iterations,
@@ -2469,40 +2569,39 @@ qkd_status qkd_reconcile_adaptive_batch(const qkd_code* c, qkd_workspace* ws, co
                                                      iterations, syndromes_match))
         return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
     if (!ad) return set_error(QKD_ERR_INVALID_ARG, "null argument");
-    if (ad->code != c) return set_error(QKD_ERR_INVALID_ARG, "the plan was created for another code");
-    if (!(known_llr > 0.0) || !std::isfinite(known_llr))
-        return set_error(QKD_ERR_INVALID_ARG, "known_llr must be finite and > 0");
-    // QKD_FLAG_ERASURES is implied; the decode parameters as qkd_reconcile_batch
-    qkd_status s = check_decode_params(max_iterations, msg_threshold, flags & ~QKD_FLAG_ERASURES);
-    if (s != QKD_OK) return s;
-    if ((flags & QKD_VARIANT_MASK) != QKD_VARIANT_SP_F64)
-        return set_error(QKD_ERR_UNSUPPORTED, "qkd_reconcile_adaptive_batch: QKD_VARIANT_SP_F64 only");
-    DeviceGuard g(c->device);
-    ws = resolve_ws(c, ws);
-    if (!ws) return set_error(QKD_ERR_OUT_OF_MEMORY, "no workspace");
-    WsSession sess(ws, (hipStream_t)stream);
-    s = ws_reserve_classes(ws, n_frames);
-    if (s != QKD_OK) return s;
-    DecodeArgs a = class_decode_args(ad, syndrome, n_frames, qber, known_llr, max_iterations, msg_threshold, flags,
-                                     payload_out, frames_out, iterations, syndromes_match, corrected);
-    const ClassArgs ca{ad->d_src_orig, ad->d_src_int, bob_payload, ws->cls};
-    return launch_decode(c, ws, a, kModeClass, flags & ~QKD_FLAG_ERASURES, (hipStream_t)stream, nullptr, nullptr,
-                         &ca);
+    return adaptive_run("qkd_reconcile_adaptive_batch", c, ws, ad, bob_payload, syndrome, n_frames, qber, known_llr,
+                        max_iterations, msg_threshold, flags, payload_out, frames_out, iterations, syndromes_match,
+                        corrected, nullptr, stream);
 }
 
-qkd_status qkd_reconcile_blind_batch(const qkd_code* c, qkd_workspace* ws, const qkd_adapt* ad,
-                                     const uint8_t* bob_payload, const uint8_t* syndrome, size_t n_frames,
-                                     double qber, double known_llr, uint32_t max_iterations, double msg_threshold,
-                                     uint32_t flags, const uint8_t* revealed, uint32_t* n_revealed,
-                                     const uint8_t* skip, uint32_t step, uint32_t max_rounds, uint8_t* payload_out,
-                                     uint8_t* frames_out, uint32_t* iterations, uint8_t* syndromes_match,
-                                     uint32_t* corrected, uint32_t* rounds, void* stream) {
+qkd_status qkd_reconcile_adaptive_verify_batch(const qkd_code* c, qkd_workspace* ws, const qkd_adapt* ad,
+                                               const uint8_t* bob_payload, const uint8_t* syndrome, size_t n_frames,
+                                               double qber, double known_llr, uint32_t max_iterations,
+                                               double msg_threshold, uint32_t flags, uint8_t* payload_out,
+                                               uint8_t* frames_out, uint32_t* iterations, uint8_t* syndromes_match,
+                                               uint32_t* corrected, uint64_t hash_seed, const uint64_t* hash_words,
+                                               uint32_t tag_bits, const uint64_t* alice_tags, uint64_t* tags_out,
+                                               uint8_t* verified, void* stream) {
     clear_error();
-    if (const char* bad = qkda::reconcile_args_error(c, bob_payload, syndrome, n_frames, qber, payload_out,
-                                                     iterations, syndromes_match))
-        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
-    if (const char* bad = qkda::reconcile_blind_args_error(ad, n_revealed, step, max_rounds))
-        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    const char* bad = qkda::reconcile_args_error(c, bob_payload, syndrome, n_frames, qber, payload_out, iterations,
+                                                 syndromes_match);
+    if (!bad) bad = qkda::reconcile_adaptive_verify_args_error(ad, tag_bits, alice_tags, tags_out, verified);
+    if (bad) return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    const ClassVerify cv{hash_seed, hash_words, tag_bits, alice_tags, tags_out, verified};
+    return adaptive_run("qkd_reconcile_adaptive_verify_batch", c, ws, ad, bob_payload, syndrome, n_frames, qber,
+                        known_llr, max_iterations, msg_threshold, flags, payload_out, frames_out, iterations,
+                        syndromes_match, corrected, &cv, stream);
+}
+
+// qkd_reconcile_blind_batch and qkd_reconcile_blind_verify_batch after their
+// argument checks; cv: the second's tags, nullptr for the first.
+static qkd_status blind_run(const char* entry, const qkd_code* c, qkd_workspace* ws, const qkd_adapt* ad,
+                            const uint8_t* bob_payload, const uint8_t* syndrome, size_t n_frames, double qber,
+                            double known_llr, uint32_t max_iterations, double msg_threshold, uint32_t flags,
+                            const uint8_t* revealed, uint32_t* n_revealed, const uint8_t* skip, uint32_t step,
+                            uint32_t max_rounds, uint8_t* payload_out, uint8_t* frames_out, uint32_t* iterations,
+                            uint8_t* syndromes_match, uint32_t* corrected, uint32_t* rounds, const ClassVerify* cv,
+                            void* stream) {
     if (ad->code != c) return set_error(QKD_ERR_INVALID_ARG, "the plan was created for another code");
     if (const char* bad = qkda::reconcile_blind_revealed_error(ad->p, revealed))
         return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
@@ -2511,7 +2610,7 @@ qkd_status qkd_reconcile_blind_batch(const qkd_code* c, qkd_workspace* ws, const
     qkd_status s = check_decode_params(max_iterations, msg_threshold, flags & ~QKD_FLAG_ERASURES);
     if (s != QKD_OK) return s;
     if ((flags & QKD_VARIANT_MASK) != QKD_VARIANT_SP_F64)
-        return set_error(QKD_ERR_UNSUPPORTED, "qkd_reconcile_blind_batch: QKD_VARIANT_SP_F64 only");
+        return set_error(QKD_ERR_UNSUPPORTED, "%s: QKD_VARIANT_SP_F64 only", entry);
     DeviceGuard g(c->device);
     ws = resolve_ws(c, ws);
     if (!ws) return set_error(QKD_ERR_OUT_OF_MEMORY, "no workspace");
@@ -2536,6 +2635,11 @@ qkd_status qkd_reconcile_blind_batch(const qkd_code* c, qkd_workspace* ws, const
     const BlindArgs ba{ad->d_rank_orig, ad->d_rank_int, revealed, n_revealed, (uint32_t)ad->p, ws->blind_list, count};
     ClassArgs ca{ad->d_src_orig, ad->d_src_int, bob_payload, ws->cls};
     ca.blind = &ba;
+    const uint64_t* vkey = nullptr;
+    if (cv) {
+        s = class_verify_key(ws, ad, *cv, (hipStream_t)stream, &vkey);
+        if (s != QKD_OK) return s;
+    }
     // every round: settle the round before and list the open frames, then
     // their class bytes and the decoder over the list (launch_decode), all on
     // the stream; the host never learns how many frames a round has
@@ -2543,18 +2647,61 @@ qkd_status qkd_reconcile_blind_batch(const qkd_code* c, qkd_workspace* ws, const
     const uint64_t useful = step ? 1 + ((uint64_t)ad->p + step - 1) / step : 1;
     const uint32_t n_rounds = (uint32_t)std::min<uint64_t>(max_rounds, useful);
     for (uint32_t t = 0; t < n_rounds; ++t) {
+        // (closed: verified when Alice's tags are given, else matched)
         const BlindRound br{t, (uint32_t)n_frames, (uint32_t)ad->p, step, skip, syndromes_match, n_revealed, rounds,
-                            ws->blind_open, ws->blind_list, count};
+                            ws->blind_open, ws->blind_list, count, (cv && cv->alice_tags) ? cv->verified : nullptr};
         QKD_HIP(launch_blind_round(br, (hipStream_t)stream));
         DecodeArgs a = class_decode_args(ad, syndrome, n_frames, qber, known_llr, max_iterations, msg_threshold,
                                          flags, payload_out, frames_out, iterations, syndromes_match, corrected);
         a.frame_list = ws->blind_list;
         a.frame_count = count;
+        if (cv) class_verify_into(a, *cv, vkey);
         s = launch_decode(c, ws, a, kModeClass, flags & ~QKD_FLAG_ERASURES, (hipStream_t)stream, nullptr, nullptr,
                           &ca);
         if (s != QKD_OK) return s;
     }
     return QKD_OK;
+}
+
+qkd_status qkd_reconcile_blind_batch(const qkd_code* c, qkd_workspace* ws, const qkd_adapt* ad,
+                                     const uint8_t* bob_payload, const uint8_t* syndrome, size_t n_frames,
+                                     double qber, double known_llr, uint32_t max_iterations, double msg_threshold,
+                                     uint32_t flags, const uint8_t* revealed, uint32_t* n_revealed,
+                                     const uint8_t* skip, uint32_t step, uint32_t max_rounds, uint8_t* payload_out,
+                                     uint8_t* frames_out, uint32_t* iterations, uint8_t* syndromes_match,
+                                     uint32_t* corrected, uint32_t* rounds, void* stream) {
+    clear_error();
+    if (const char* bad = qkda::reconcile_args_error(c, bob_payload, syndrome, n_frames, qber, payload_out,
+                                                     iterations, syndromes_match))
+        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    if (const char* bad = qkda::reconcile_blind_args_error(ad, n_revealed, step, max_rounds))
+        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    return blind_run("qkd_reconcile_blind_batch", c, ws, ad, bob_payload, syndrome, n_frames, qber, known_llr,
+                     max_iterations, msg_threshold, flags, revealed, n_revealed, skip, step, max_rounds, payload_out,
+                     frames_out, iterations, syndromes_match, corrected, rounds, nullptr, stream);
+}
+
+qkd_status qkd_reconcile_blind_verify_batch(const qkd_code* c, qkd_workspace* ws, const qkd_adapt* ad,
+                                            const uint8_t* bob_payload, const uint8_t* syndrome, size_t n_frames,
+                                            double qber, double known_llr, uint32_t max_iterations,
+                                            double msg_threshold, uint32_t flags, const uint8_t* revealed,
+                                            uint32_t* n_revealed, const uint8_t* skip, uint32_t step,
+                                            uint32_t max_rounds, uint8_t* payload_out, uint8_t* frames_out,
+                                            uint32_t* iterations, uint8_t* syndromes_match, uint32_t* corrected,
+                                            uint32_t* rounds, uint64_t hash_seed, const uint64_t* hash_words,
+                                            uint32_t tag_bits, const uint64_t* alice_tags, uint64_t* tags_out,
+                                            uint8_t* verified, void* stream) {
+    clear_error();
+    const char* bad = qkda::reconcile_args_error(c, bob_payload, syndrome, n_frames, qber, payload_out, iterations,
+                                                 syndromes_match);
+    if (!bad)
+        bad = qkda::reconcile_blind_verify_args_error(ad, n_revealed, step, max_rounds, tag_bits, alice_tags,
+                                                      tags_out, verified);
+    if (bad) return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    const ClassVerify cv{hash_seed, hash_words, tag_bits, alice_tags, tags_out, verified};
+    return blind_run("qkd_reconcile_blind_verify_batch", c, ws, ad, bob_payload, syndrome, n_frames, qber, known_llr,
+                     max_iterations, msg_threshold, flags, revealed, n_revealed, skip, step, max_rounds, payload_out,
+                     frames_out, iterations, syndromes_match, corrected, rounds, &cv, stream);
 }
 
 static VerifyArgs verify_args(const qkd_code* c, uint64_t hash_seed, const uint64_t* hash_words, uint32_t tag_bits,
@@ -2598,6 +2745,24 @@ qkd_status qkd_verify_tags_batch(const qkd_code* c, const uint8_t* bits, size_t 
     DeviceGuard g(c->device);
     const VerifyArgs v = verify_args(c, hash_seed, hash_words, tag_bits, nullptr, tags, nullptr, nullptr);
     QKD_HIP(launch_verify_tags(bits, (uint32_t)c->n, (uint32_t)n_frames, v, (hipStream_t)stream));
+    return QKD_OK;
+}
+
+qkd_status qkd_adapt_verify_tags_batch(const qkd_adapt* ad, const uint8_t* payload, size_t n_frames,
+                                       uint64_t hash_seed, const uint64_t* hash_words, uint32_t tag_bits,
+                                       uint64_t* tags, void* stream) {
+    clear_error();
+    if (const char* bad = qkda::adapt_verify_tags_args_error(ad, payload, n_frames, tag_bits, tags))
+        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    DeviceGuard g(ad->device);
+    // the byte-key tag kernel over the payload: positions are payload indices
+    VerifyArgs v{};
+    v.seed = hash_seed;
+    v.words = hash_words;
+    v.key_words = (uint32_t)qkdv::verify_key_words(ad->n_payload);
+    v.mask = qkdv::verify_tag_mask(tag_bits);
+    v.tags_out = tags;
+    QKD_HIP(launch_verify_tags(payload, (uint32_t)ad->n_payload, (uint32_t)n_frames, v, (hipStream_t)stream));
     return QKD_OK;
 }
 

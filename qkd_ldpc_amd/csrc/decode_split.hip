@@ -1394,10 +1394,15 @@ constexpr bool sole_decode_args(void (*)(A...)) {
 }
 // ERA: the binary64 rule extended to zero LLRs (QKD_FLAG_ERASURES; edge_out),
 // exact iterations only. kModeClass (qkd_reconcile_adaptive_batch) always has it.
-template <int MODE, int RULE, int DC, bool CLAMP, int SPEC, bool LONG = false, bool ERA = false>
+// VFY (kModeClass): the payload's verification tag from the output loop
+// (DecodeArgs::vkey). A template parameter, not a branch on vkey: the branch
+// put a VGPR of every class-mode instantiation in scratch
+// (profiles/adapt_verify_kernel_resources.txt).
+template <int MODE, int RULE, int DC, bool CLAMP, int SPEC, bool LONG = false, bool ERA = false, bool VFY = false>
 __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
-    static_assert(sole_decode_args(&decode_split_kernel<MODE, RULE, DC, CLAMP, SPEC, LONG, ERA>),
+    static_assert(sole_decode_args(&decode_split_kernel<MODE, RULE, DC, CLAMP, SPEC, LONG, ERA, VFY>),
                   "kernel_args(): DecodeArgs must be the only kernel parameter");
+    static_assert(!VFY || MODE == kModeClass, "payload tags: the class-byte mode");
     static_assert(!ERA || (RULE == kRuleSp64 && SPEC == 0 && !LONG), "erasure rule: binary64, exact iterations");
     static_assert(MODE != kModeClass || ERA, "class bytes: always with the erasure rule");
     static_assert(!LONG || (MODE == kModeKeys && RULE == kRuleSp64 && SPEC == 0), "long codes: exact keys path");
@@ -2079,17 +2084,28 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
             // for punctured and shortened bits), its flips against Bob's
             // payload (class bit 0) summed through ctl[7], and the whole
             // decision where asked for
+            // Key verification (VFY; DecodeArgs::vkey): the payload's tag from
+            // the same decisions, each wave's XOR left in the product rows (free
+            // since the last check phase, and until the next frame's first one)
+            // for thread 0 after the barrier below.
             uint32_t nflip = 0;
+            const uint64_t* const vkey = VFY ? ea->vkey : nullptr;
+            uint64_t vacc = 0;
             for (int i = etid; i < c.n; i += kDecodeBlock) {
                 const uint8_t z = (uint8_t)((zw[i >> 6] >> (i & 63)) & 1u);
                 const int32_t k = ea->src[i];
                 if (k >= 0) {
                     ea->payload_out[(size_t)f * ea->n_payload + (uint32_t)k] = z;
                     nflip += (uint32_t)(z ^ (ea->cls[(size_t)f * c.n + i] & 1u));
+                    if constexpr (VFY) vacc ^= class_verify_window(vkey, (uint32_t)k, z);
                 }
                 if (ea->bits_out) ea->bits_out[(size_t)f * c.n + c.perm[i]] = z;
             }
             if (ea->flips && nflip) atomicAdd(ctl + 7, nflip);
+            if constexpr (VFY) {
+                const uint64_t wx = wave_xor64(vacc);
+                if (lane == 0) reinterpret_cast<uint64_t*>(smem + L.tval)[wave] = wx;
+            }
         } else if (ea->bits_out) {
             for (int i = etid; i < c.n; i += kDecodeBlock)
                 ea->bits_out[(size_t)f * c.n + c.perm[i]] = (uint8_t)((zw[i >> 6] >> (i & 63)) & 1u);
@@ -2116,6 +2132,9 @@ __global__ QKD_SPLIT_BOUNDS void decode_split_kernel(DecodeArgs a) {
             ea->flips[f] = ctl[7];
             ctl[7] = 0;
         }
+        if (VFY && tid == 0)
+            class_verify_finish(reinterpret_cast<const uint64_t*>(smem + L.tval), ea->vmask, ea->vtags, ea->valice,
+                                ea->vok, f, done);
     }
     pc.flush();
 }
@@ -2859,19 +2878,22 @@ DecodeFn pick_split_long(bool clamp, int max_dc, int* dc) {
 
 // the erasure rule's kernels (binary64, exact iterations): the LLR path with
 // QKD_FLAG_ERASURES, and the class-byte path
-template <int MODE, bool CLAMP>
+template <int MODE, bool CLAMP, bool VFY = false>
 static DecodeFn pick_split_era_dc(int max_dc, int* dc) {
-    if (max_dc <= 4) { *dc = 4; return decode_split_kernel<MODE, kRuleSp64, 4, CLAMP, 0, false, true>; }
-    if (max_dc <= 6) { *dc = 6; return decode_split_kernel<MODE, kRuleSp64, 6, CLAMP, 0, false, true>; }
-    if (max_dc <= 8) { *dc = 8; return decode_split_kernel<MODE, kRuleSp64, 8, CLAMP, 0, false, true>; }
-    if (max_dc <= 16) { *dc = 16; return decode_split_kernel<MODE, kRuleSp64, 16, CLAMP, 0, false, true>; }
+    if (max_dc <= 4) { *dc = 4; return decode_split_kernel<MODE, kRuleSp64, 4, CLAMP, 0, false, true, VFY>; }
+    if (max_dc <= 6) { *dc = 6; return decode_split_kernel<MODE, kRuleSp64, 6, CLAMP, 0, false, true, VFY>; }
+    if (max_dc <= 8) { *dc = 8; return decode_split_kernel<MODE, kRuleSp64, 8, CLAMP, 0, false, true, VFY>; }
+    if (max_dc <= 16) { *dc = 16; return decode_split_kernel<MODE, kRuleSp64, 16, CLAMP, 0, false, true, VFY>; }
     *dc = 64;
-    return decode_split_kernel<MODE, kRuleSp64, 64, CLAMP, 0, false, true>;
+    return decode_split_kernel<MODE, kRuleSp64, 64, CLAMP, 0, false, true, VFY>;
 }
 
-DecodeFn pick_split_decode(int mode, int rule, bool clamp, int max_dc, int* dc, bool era) {
+DecodeFn pick_split_decode(int mode, int rule, bool clamp, int max_dc, int* dc, bool era, bool vfy) {
     if (era || mode == kModeClass) {
         if (rule != kRuleSp64) return nullptr;
+        if (mode == kModeClass && vfy)
+            return clamp ? pick_split_era_dc<kModeClass, true, true>(max_dc, dc)
+                         : pick_split_era_dc<kModeClass, false, true>(max_dc, dc);
         if (mode == kModeClass)
             return clamp ? pick_split_era_dc<kModeClass, true>(max_dc, dc)
                          : pick_split_era_dc<kModeClass, false>(max_dc, dc);

@@ -1,7 +1,8 @@
 // qkd_args.h — host-only argument checks of the batched entry points, free of
 // HIP so that a stand-alone host program can exercise them
 // (tests/native/reconcile_args_check.cpp, tests/native/verify_hash_check.cpp,
-// tests/native/privacy_hash_check.cpp, tests/native/blind_args_check.cpp).
+// tests/native/privacy_hash_check.cpp, tests/native/blind_args_check.cpp,
+// tests/native/adapt_verify_args_check.cpp).
 #pragma once
 
 #include <stddef.h>
@@ -66,6 +67,35 @@ inline const char* reconcile_verify_args_error(uint32_t tag_bits, const uint64_t
     if (alice_tags && !verified) return "alice_tags given without verified";
     if (!alice_tags && verified) return "verified given without alice_tags";
     return nullptr;
+}
+
+// qkd_adapt_verify_tags_batch's arguments: qkd_verify_tags_batch's, with the
+// plan in the code's place.
+inline const char* adapt_verify_tags_args_error(const void* adapt, const uint8_t* payload, size_t n_frames,
+                                                uint32_t tag_bits, const uint64_t* tags) {
+    return verify_tags_args_error(adapt, payload, n_frames, tag_bits, tags);
+}
+
+// What qkd_reconcile_adaptive_verify_batch adds to
+// qkd_reconcile_adaptive_batch's arguments (checked after
+// reconcile_args_error, before the plan is looked at): the plan, then
+// reconcile_verify_args_error's rules.
+inline const char* reconcile_adaptive_verify_args_error(const void* adapt, uint32_t tag_bits,
+                                                        const uint64_t* alice_tags, const uint64_t* tags_out,
+                                                        const uint8_t* verified) {
+    if (!adapt) return "null argument";
+    return reconcile_verify_args_error(tag_bits, alice_tags, tags_out, verified);
+}
+
+// What qkd_reconcile_blind_verify_batch adds to qkd_reconcile_adaptive_batch's
+// arguments, the same way: reconcile_blind_args_error's rules first, then
+// reconcile_verify_args_error's.
+inline const char* reconcile_blind_verify_args_error(const void* adapt, const uint32_t* n_revealed, uint32_t step,
+                                                     uint32_t max_rounds, uint32_t tag_bits,
+                                                     const uint64_t* alice_tags, const uint64_t* tags_out,
+                                                     const uint8_t* verified) {
+    if (const char* bad = reconcile_blind_args_error(adapt, n_revealed, step, max_rounds)) return bad;
+    return reconcile_verify_args_error(tag_bits, alice_tags, tags_out, verified);
 }
 
 // qkd_privacy_amplify_batch's arguments, the same way. hash_words and keep may

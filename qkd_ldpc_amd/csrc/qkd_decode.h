@@ -224,7 +224,55 @@ struct DecodeArgs {
     uint8_t* payload_out;
     uint32_t n_payload;
     uint32_t* flips;
+    // kModeClass, key verification (qkd_reconcile_adaptive_verify_batch,
+    // qkd_reconcile_blind_verify_batch; vkey == nullptr: none, and the kernel
+    // instantiation without it, the VFY template parameter): the payload's
+    // tag (qkd_verify.h, positions = payload indices) taken in the loop that
+    // writes payload_out. vkey: the qkdv::verify_key_words(n_payload) words of
+    // the key string on the device, exactly that many (the caller's, or the
+    // workspace's expansion of the seed); vmask: qkdv::verify_tag_mask(tag_bits).
+    // vtags[f] (or nullptr) = the masked tag; with valice, vok[f] = sp_ok[f] &&
+    // the masked tag equals valice[f]'s.
+    const uint64_t* vkey;
+    uint64_t vmask;
+    const uint64_t* valice;
+    uint64_t* vtags;
+    uint8_t* vok;
 };
+
+// kModeClass with DecodeArgs::vkey: the payload decision d at payload index k
+// adds W(k) & -(d) to the thread's XOR (the per-position form of qkd_verify.h).
+// At k & 63 == 0 the window is R[k >> 6] itself and the word after it may lie
+// past the string's end: the low word is read twice instead.
+__device__ __forceinline__ uint64_t class_verify_window(const uint64_t* __restrict__ R, uint32_t k, uint32_t d) {
+    const uint32_t w = k >> 6, s = k & 63u;
+    const uint64_t lo = R[w], hi = R[w + (s ? 1u : 0u)];
+    return qkdv::verify_window(lo, hi, s) & (0ull - (uint64_t)d);
+}
+
+// The XOR of v over the lanes of a wave, in every lane.
+__device__ __forceinline__ uint64_t wave_xor64(uint64_t v) {
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        lo ^= (uint32_t)__shfl_xor((int)lo, s);
+        hi ^= (uint32_t)__shfl_xor((int)hi, s);
+    }
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// Thread 0, after the barrier that follows the waves' stores of their XORs to
+// red[0 .. kDecodeBlock / 64): the frame's tag out and, against Alice's, the
+// verdict (DecodeArgs::vmask, vtags, valice, vok).
+__device__ __forceinline__ void class_verify_finish(const uint64_t* red, uint64_t mask, uint64_t* vtags,
+                                                    const uint64_t* valice, uint8_t* vok, uint32_t f, bool sp_ok) {
+    uint64_t t = 0;
+#pragma unroll
+    for (int w = 0; w < kDecodeBlock / 64; ++w) t ^= red[w];
+    t &= mask;
+    if (vtags) vtags[f] = t;
+    if (valice) vok[f] = (sp_ok && ((t ^ valice[f]) & mask) == 0) ? 1 : 0;
+}
 
 // kModeClass: the channel LLR of a class byte (selects on registers: no table)
 __device__ __forceinline__ double class_llr(uint32_t cl, double log_p, double known) {
@@ -761,7 +809,9 @@ using DecodeFn = void (*)(DecodeArgs);
 // decode_split.hip: the split-store kernel for (mode, rule in {kRuleSp64,
 // kRuleSp32}, clamp, check-degree bucket); *dc receives the bucket.
 // era (binary64 rule, kModeLlr; kModeClass always): the erasure rule's kernels.
-DecodeFn pick_split_decode(int mode, int rule, bool clamp, int max_dc, int* dc, bool era = false);
+// vfy (kModeClass): the instantiations that take the payload's verification
+// tag (DecodeArgs::vkey != nullptr).
+DecodeFn pick_split_decode(int mode, int rule, bool clamp, int max_dc, int* dc, bool era = false, bool vfy = false);
 // the exact keys-path split kernel for codes past kMaxBitsSplit bits (up to
 // kMaxBitsSplitLong; check degree <= 16): the interleaved decoder's hand-offs
 DecodeFn pick_split_long(bool clamp, int max_dc, int* dc);
@@ -838,7 +888,13 @@ struct BlindRound {
     uint8_t* open;                   // F: workspace
     uint32_t* list;
     uint32_t* count;
+    // qkd_reconcile_blind_verify_batch with alice_tags: the decoder's verified
+    // (F); a frame is then closed by it instead of by sp_ok. nullptr otherwise.
+    const uint8_t* verified = nullptr;
 };
 hipError_t launch_blind_round(const BlindRound& r, hipStream_t stream);
+// out[0 .. words) = the seeded key string of the verification hash
+// (qkdv::verify_key_word), once per verifying class-mode call
+hipError_t launch_verify_expand(uint64_t seed, uint32_t words, uint64_t* out, hipStream_t stream);
 
 }  // namespace qkd

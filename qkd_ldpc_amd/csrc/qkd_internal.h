@@ -207,6 +207,10 @@ struct qkd_workspace {
     uint32_t* blind_list = nullptr;
     uint8_t* blind_open = nullptr;
     size_t blind_frames = 0;
+    // qkd_reconcile_adaptive_verify_batch / qkd_reconcile_blind_verify_batch
+    // with the seeded key string: its words, expanded once per call
+    uint64_t* vkey = nullptr;
+    size_t vkey_words = 0;
     // qkd_debug_decoder_timing: while on, HIP events bracket every decoder
     // launch on its stream (pairs recorded, read back on collection)
     bool time_decoder = false;
