@@ -558,6 +558,59 @@ QKD_API qkd_status qkd_privacy_amplify_batch(int device, const uint8_t *keys, si
                                              const uint64_t *hash_words, const uint8_t *keep,
                                              uint64_t *out_words, void *stream);
 
+/* ---- long-block privacy amplification ----------------------------------------
+ * The same hash, bit for bit, for blocks past QKD_PRIVACY_MAX_BITS: a
+ * finite-key analysis sets out_bits from the block length and wants blocks of
+ * 10^7 to 10^8 bits. Where qkd_privacy_amplify_batch does n_in * out_bits
+ * work, this entry takes the hash as a cyclic convolution of the input with
+ * the key string by number-theoretic transforms modulo 15 * 2^27 + 1, of
+ * length T = the power of two at or above n_in + L - 1 (at least 64):
+ * O(T log T). The range is 1 <= out_bits <= n_in with
+ * n_in + out_bits - 1 <= QKD_PRIVACY_LONG_MAX_BITS, e.g. 2^26 + 1 bits hashed
+ * to 2^26, or 10^8 to 3.4 * 10^7. Every shape both entries accept gives the
+ * same words from both. The key string is hash_words[Wp] or the seeded form as
+ * above (a computational stand-in, NOT an information-theoretic one), Wp =
+ * qkd_privacy_long_key_words(n_in, L) = ceil((n_in + L - 1) / 64), equal to
+ * qkd_privacy_key_words wherever that is defined. */
+#define QKD_PRIVACY_LONG_MAX_BITS (1u << 27)   /* n_in + out_bits - 1 */
+
+/* Wp of the long form; 0 unless 1 <= out_bits <= n_in and
+ * n_in + out_bits - 1 <= QKD_PRIVACY_LONG_MAX_BITS. Host only. */
+QKD_API size_t qkd_privacy_long_key_words(uint32_t n_in, uint32_t out_bits);
+
+/* The Wp words the seeded form uses, into host memory: the words of
+ * qkd_privacy_expand_key, over the long form's range. Host only. */
+QKD_API qkd_status qkd_privacy_long_expand_key(uint64_t hash_seed, uint32_t n_in, uint32_t out_bits,
+                                               uint64_t *words_host);
+
+/* The bytes of device scratch one call needs (two arrays of T 32-bit residues
+ * and a twiddle table of about 2 sqrt(T) entries: 8 T bytes and a little, about
+ * 1 GiB at T = 2^27); 0 for sizes outside the range. Depends on the sizes
+ * only, not on n_blocks. Host only. */
+QKD_API size_t qkd_privacy_long_scratch_bytes(uint32_t n_in, uint32_t out_bits);
+
+/* out_words[n_blocks * Wo] = the hashes of keys[n_blocks * n_in] (0/1 bytes on
+ * `device`, only byte & 1 counts; contiguous blocks, base address of any
+ * alignment), Wo = ceil(out_bits / 64), packed as by qkd_privacy_amplify_batch.
+ * keep[n_blocks] (may be NULL) is per BLOCK: a block with keep[b] == 0 gets Wo
+ * zero words. A caller who wants only the verified frames of a block compacts
+ * them into the block first; Alice must hash the same frames, so the block's
+ * length has to be agreed with her. scratch: device memory of at least
+ * qkd_privacy_long_scratch_bytes(n_in, out_bits) bytes, any alignment, any
+ * contents; the blocks of a call run one after another through it, and the
+ * key string's transform is taken once per call. out_words is fully
+ * overwritten and nothing is written outside it and the scratch.
+ * QKD_ERR_INVALID_ARG, before any device work, for NULL keys, out_words or
+ * scratch, n_blocks of 0 or >= 2^32, sizes outside the range, scratch_bytes
+ * below qkd_privacy_long_scratch_bytes, or a bad device. Kernel launches on the
+ * stream only: no allocation, no host copy, no synchronisation, no atomics
+ * (the same bits on every run); capturable in a graph. */
+QKD_API qkd_status qkd_privacy_amplify_long_batch(int device, const uint8_t *keys, size_t n_blocks,
+                                                  uint32_t n_in, uint32_t out_bits, uint64_t hash_seed,
+                                                  const uint64_t *hash_words, const uint8_t *keep,
+                                                  uint64_t *out_words, void *scratch, size_t scratch_bytes,
+                                                  void *stream);
+
 /* generate_random_bit_array + introduce_errors (array_and_matrix_operations.cpp:424-460)
  * for frame k seeded with seeds[k] + seed_offset (simulation.cpp:163,247),
  * on the device. alice/bob [F*N] 0/1 bytes; exact_qber[F] may be NULL.
@@ -643,6 +696,10 @@ QKD_API qkd_status qkd_counters_merge(const qkd_counters *records, size_t n_reco
  *                              tables in LDS (the default; table1 | table2 |
  *                              table4 fix its outputs per lane, which it
  *                              otherwise chooses from the launch's size)
+ *   QKD_PRIVACY_NTT_LOG2 <S>   (ws == NULL) 3..13: log2 of the residues one
+ *                              workgroup of qkd_privacy_amplify_long_batch
+ *                              transforms in LDS (default 13); a small S
+ *                              runs the many-pass paths at a few hundred points
  * An unknown name fails with QKD_ERR_INVALID_ARG. Thread-safe. No reference
  * counterpart (the reference's CFG fields are the decode parameters). */
 QKD_API qkd_status qkd_debug_set_option(qkd_workspace *ws, const char *name, const char *value);

@@ -14,6 +14,7 @@ src/array_and_matrix_operations.hpp) with batched, device-resident arrays:
   its decode step alone, Bob's side of a link      reconcile(H, bob, syndrome, qber, ...)
   (no counterpart) key verification tags            verify_tags(H, bits, ...), reconcile(..., alice_tags=)
   (no counterpart) privacy amplification            privacy_amplify(keys, out_bits, ..., keep=verified)
+  (no counterpart) ... of blocks up to 2^27 bits     privacy_amplify_long(keys, out_bits, ..., scratch=)
   (no counterpart) punctured / shortened frames     AdaptPlan, adapt_embed, adapt_extract,
                                                     reconcile_adaptive(H, plan, bob_payload, ...)
   (no counterpart) blind reconciliation             reconcile_blind(H, plan, bob_payload, ..., revealed=)
@@ -49,6 +50,7 @@ __all__ = [
     "spec_replays", "check_lanes", "interactive_simulation", "reconcile", "ReconcileResult",
     "verify_key_words", "verify_expand_key", "verify_tags",
     "privacy_key_words", "privacy_expand_key", "privacy_amplify",
+    "privacy_long_key_words", "privacy_long_expand_key", "privacy_long_scratch_bytes", "privacy_amplify_long",
     "AdaptPlan", "adapt_positions", "adapt_embed", "adapt_extract", "reconcile_adaptive",
     "reconcile_blind", "BlindResult",
 ]
@@ -781,7 +783,8 @@ def privacy_amplify(keys, out_bits: int, hash_seed: int = 0, hash_words=None, ke
     universal form) or, without them, expanded from hash_seed (a computational stand-in).
     It must be independent of the verification hash's string. keep ([F] uint8, typically
     ReconcileResult.verified): frames with 0 get all-zero words. To hash B corrected
-    frames as one block, pass bits.view(F // B, B * N)."""
+    frames as one block, pass bits.view(F // B, B * N). Past n_in = 2^20 the call goes to
+    privacy_amplify_long (the same bits by transforms; keep is then per block)."""
     _need_cuda(keys, torch.uint8, "keys")
     if keys.dim() != 2 or keys.shape[0] < 1 or keys.shape[1] < 1:
         raise QkdError(N.ERR_INVALID_ARG, f"keys must have shape [F, n_in], got {list(keys.shape)}")
@@ -789,8 +792,8 @@ def privacy_amplify(keys, out_bits: int, hash_seed: int = 0, hash_words=None, ke
     if not isinstance(out_bits, int) or not 1 <= out_bits <= n_in:
         raise QkdError(N.ERR_INVALID_ARG, f"out_bits must be in 1..{n_in}")
     wp = privacy_key_words(n_in, out_bits)
-    if wp == 0:
-        raise QkdError(N.ERR_INVALID_ARG, "n_in exceeds 2^20 bits")
+    if wp == 0:            # n_in exceeds 2^20 bits: the long form's range
+        return privacy_amplify_long(keys, out_bits, hash_seed, hash_words, keep, stream=stream)
     dev = _Device(keys.device.index)
     if hash_words is not None:
         _need_tags(hash_words, wp, "hash_words", dev)
@@ -801,6 +804,77 @@ def privacy_amplify(keys, out_bits: int, hash_seed: int = 0, hash_words=None, ke
     N.check(N.lib().qkd_privacy_amplify_batch(dev.device, _ptr(keys), f, n_in, out_bits, seed, _ptr(hash_words),
                                               _ptr(keep), _ptr(out), _stream(stream, dev.device)))
     return out
+
+
+def privacy_long_key_words(n_in: int, out_bits: int) -> int:
+    """Wp = ceil((n_in + out_bits - 1) / 64) over the long form's range
+    (qkd_privacy_long_key_words); 0 unless 1 <= out_bits <= n_in and
+    n_in + out_bits - 1 <= 2^27."""
+    if not (0 <= n_in < 2**32 and 0 <= out_bits < 2**32):
+        return 0
+    return int(N.lib().qkd_privacy_long_key_words(n_in, out_bits))
+
+
+def privacy_long_expand_key(hash_seed: int, n_in: int, out_bits: int) -> np.ndarray:
+    """The Wp words the seeded form uses over the long form's range
+    (qkd_privacy_long_expand_key), as a numpy uint64 array."""
+    w = privacy_long_key_words(n_in, out_bits)
+    if w == 0:
+        raise QkdError(N.ERR_INVALID_ARG, "need 1 <= out_bits <= n_in and n_in + out_bits - 1 <= 2^27")
+    out = np.zeros(w, np.uint64)
+    N.check(N.lib().qkd_privacy_long_expand_key(hash_seed & (2**64 - 1), n_in, out_bits, out.ctypes.data))
+    return out
+
+
+def privacy_amplify_long(keys, out_bits: int, hash_seed: int = 0, hash_words=None, keep=None, scratch=None,
+                         stream=None):
+    """Long-block privacy amplification (qkd_privacy_amplify_long_batch): the hash of
+    privacy_amplify, bit for bit, by number-theoretic transforms, for keys [B, n_in] uint8
+    with 1 <= out_bits <= n_in and n_in + out_bits - 1 <= 2^27; returns
+    [B, ceil(out_bits / 64)] int64 bit patterns. hash_words holds
+    privacy_long_key_words(n_in, out_bits) words; the seeded string is a computational
+    stand-in. keep ([B] uint8) is per block: a block with 0 gets all-zero words (to hash only
+    the verified frames of a block, compact them first, to a length agreed with Alice).
+    scratch: a uint8 device tensor of at least privacy_long_scratch_bytes(n_in, out_bits)
+    bytes (about 8 bytes per bit of the power of two at or above n_in + out_bits - 1), to
+    reuse one allocation over calls; without it the wrapper allocates one for the call."""
+    _need_cuda(keys, torch.uint8, "keys")
+    if keys.dim() != 2 or keys.shape[0] < 1 or keys.shape[1] < 1:
+        raise QkdError(N.ERR_INVALID_ARG, f"keys must have shape [B, n_in], got {list(keys.shape)}")
+    f, n_in = int(keys.shape[0]), int(keys.shape[1])
+    if not isinstance(out_bits, int) or not 1 <= out_bits <= n_in:
+        raise QkdError(N.ERR_INVALID_ARG, f"out_bits must be in 1..{n_in}")
+    wp = privacy_long_key_words(n_in, out_bits)
+    if wp == 0:
+        raise QkdError(N.ERR_INVALID_ARG, "n_in + out_bits - 1 exceeds 2^27 bits")
+    dev = _Device(keys.device.index)
+    if hash_words is not None:
+        _need_tags(hash_words, wp, "hash_words", dev)
+    if keep is not None:
+        _need_vec(keep, torch.uint8, f, "keep", dev)
+    need = privacy_long_scratch_bytes(n_in, out_bits)
+    ts = _torch_stream(stream, dev.device)
+    if scratch is None:
+        # allocated under the launch stream, so that the allocator hands the memory on
+        # only to work that stream orders after this call's kernels
+        with torch.cuda.stream(ts):
+            scratch = torch.empty(need, dtype=torch.uint8, device=keys.device)
+    else:
+        _need_cuda(scratch, torch.uint8, "scratch", dev)
+    seed = (0 if hash_seed is None else int(hash_seed)) & (2**64 - 1)
+    out = torch.empty(f, (out_bits + 63) // 64, dtype=torch.int64, device=keys.device)
+    N.check(N.lib().qkd_privacy_amplify_long_batch(dev.device, _ptr(keys), f, n_in, out_bits, seed, _ptr(hash_words),
+                                                   _ptr(keep), _ptr(out), _ptr(scratch), scratch.numel(),
+                                                   int(ts.cuda_stream)))
+    return out
+
+
+def privacy_long_scratch_bytes(n_in: int, out_bits: int) -> int:
+    """The bytes of scratch privacy_amplify_long needs (qkd_privacy_long_scratch_bytes);
+    0 for sizes outside its range."""
+    if not (0 <= n_in < 2**32 and 0 <= out_bits < 2**32):
+        return 0
+    return int(N.lib().qkd_privacy_long_scratch_bytes(n_in, out_bits))
 
 
 def keygen(H: HMatrix, seeds, q_nominal: float, seed_offset: int = 0, workspace=None,

@@ -12,6 +12,7 @@
 #include <sstream>
 
 #include "qkd_internal.h"
+#include "qkd_ntt.h"
 #include "qkd_plan.h"
 #include "qkd_privacy.h"
 #include "qkd_rng.h"
@@ -38,7 +39,7 @@ static const char* const kDebugOptions[] = {
     "QKD_SPEC_CAP", "QKD_SPEC_CKPT", "QKD_CKPT_UNSAT", "QKD_SPEC_POLICY", "QKD_FOLD_TABLE",
     "QKD_DECODE_KERNEL", "QKD_MINSUM_STORE", "QKD_DECODE_GRID", "QKD_SPLIT_BUDGET", "QKD_C2B_PAD",
     "QKD_ILV", "QKD_ILV_GRID", "QKD_KEYGEN", "QKD_SYN_SLICED", "QKD_SYN_BYTES", "QKD_BIT_ORDER",
-    "QKD_PHASE_TIMING", "QKD_CHECK_LANES", "QKD_PRIVACY_KERNEL"};
+    "QKD_PHASE_TIMING", "QKD_CHECK_LANES", "QKD_PRIVACY_KERNEL", "QKD_PRIVACY_NTT_LOG2"};
 static std::mutex g_dbg_mu;                            // guards g_dbg and every workspace's dbg
 static std::map<std::string, std::string> g_dbg;
 
@@ -899,6 +900,19 @@ qkd_status qkd_privacy_expand_key(uint64_t hash_seed, uint32_t n_in, uint32_t ou
     if (!words_host) return set_error(QKD_ERR_INVALID_ARG, "null argument");
     const size_t w = qkdv::privacy_key_words(n_in, out_bits);
     if (w == 0) return set_error(QKD_ERR_INVALID_ARG, "need 1 <= out_bits <= n_in <= QKD_PRIVACY_MAX_BITS");
+    for (size_t k = 0; k < w; ++k) words_host[k] = qkdv::verify_key_word(hash_seed, k);
+    return QKD_OK;
+}
+
+size_t qkd_privacy_long_key_words(uint32_t n_in, uint32_t out_bits) { return qkdn::long_key_words(n_in, out_bits); }
+
+qkd_status qkd_privacy_long_expand_key(uint64_t hash_seed, uint32_t n_in, uint32_t out_bits, uint64_t* words_host) {
+    clear_error();
+    if (!words_host) return set_error(QKD_ERR_INVALID_ARG, "null argument");
+    const size_t w = qkdn::long_key_words(n_in, out_bits);
+    if (w == 0)
+        return set_error(QKD_ERR_INVALID_ARG,
+                         "need 1 <= out_bits <= n_in and n_in + out_bits - 1 <= QKD_PRIVACY_LONG_MAX_BITS");
     for (size_t k = 0; k < w; ++k) words_host[k] = qkdv::verify_key_word(hash_seed, k);
     return QKD_OK;
 }

@@ -2,12 +2,13 @@
 // HIP so that a stand-alone host program can exercise them
 // (tests/native/reconcile_args_check.cpp, tests/native/verify_hash_check.cpp,
 // tests/native/privacy_hash_check.cpp, tests/native/blind_args_check.cpp,
-// tests/native/adapt_verify_args_check.cpp).
+// tests/native/adapt_verify_args_check.cpp, tests/native/ntt_mod_check.cpp).
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
 
+#include "qkd_ntt.h"
 #include "qkd_privacy.h"
 
 namespace qkda {
@@ -107,6 +108,22 @@ inline const char* privacy_amplify_args_error(const uint8_t* keys, size_t n_fram
     if (n_frames > 0xffffffffull) return "n_frames too large";
     if (n_in < 1 || n_in > qkdv::kPrivacyMaxBits) return "n_in must be in 1..QKD_PRIVACY_MAX_BITS";
     if (out_bits < 1 || out_bits > n_in) return "out_bits must be in 1..n_in";
+    return nullptr;
+}
+
+// qkd_privacy_amplify_long_batch's arguments, the same way: a block in the
+// frame's place, the long form's size range, and the scratch.
+inline const char* privacy_amplify_long_args_error(const uint8_t* keys, size_t n_blocks, uint32_t n_in,
+                                                   uint32_t out_bits, const uint64_t* out_words, const void* scratch,
+                                                   size_t scratch_bytes) {
+    if (!keys || !out_words || !scratch) return "null argument";
+    if (n_blocks == 0) return "n_blocks must be > 0";
+    if (n_blocks > 0xffffffffull) return "n_blocks too large";
+    if (n_in < 1 || n_in > qkdn::kLongMaxBits) return "n_in must be in 1..QKD_PRIVACY_LONG_MAX_BITS";
+    if (out_bits < 1 || out_bits > n_in) return "out_bits must be in 1..n_in";
+    if (qkdn::long_key_words(n_in, out_bits) == 0) return "n_in + out_bits - 1 exceeds QKD_PRIVACY_LONG_MAX_BITS";
+    if (scratch_bytes < qkdn::long_scratch_bytes(n_in, out_bits))
+        return "scratch_bytes is below qkd_privacy_long_scratch_bytes(n_in, out_bits)";
     return nullptr;
 }
 

@@ -33,7 +33,8 @@
 
 namespace qkdv {
 
-// n_in and out_bits at most this (QKD_PRIVACY_MAX_BITS of the ABI header)
+// n_in and out_bits at most this (QKD_PRIVACY_MAX_BITS of the ABI header);
+// longer blocks take the same hash by transforms (qkd_ntt.h, privacy_ntt.hip)
 constexpr uint32_t kPrivacyMaxBits = 1u << 20;
 
 // Wp: the words of the key string, 0 for arguments outside
