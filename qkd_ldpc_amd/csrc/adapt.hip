@@ -191,16 +191,6 @@ hipError_t launch_verify_expand(uint64_t seed, uint32_t words, uint64_t* out, hi
     return hipGetLastError();
 }
 
-static void adapt_free(qkd_adapt* a) {
-    DeviceGuard g(a->device);
-    if (a->d_rank_orig) (void)hipFree(a->d_rank_orig);
-    if (a->d_rank_int) (void)hipFree(a->d_rank_int);
-    if (a->d_src_orig) (void)hipFree(a->d_src_orig);
-    if (a->d_src_int) (void)hipFree(a->d_src_int);
-    if (a->d_emb) (void)hipFree(a->d_emb);
-    delete a;
-}
-
 static qkd_status adapt_build(qkd_adapt* a, const qkd_code* c, const int32_t* punctured, int32_t p,
                               const int32_t* shortened, int32_t s) {
     const int32_t n = c->n;
@@ -216,7 +206,7 @@ static qkd_status adapt_build(qkd_adapt* a, const qkd_code* c, const int32_t* pu
         if (emb[pos] != 0) return set_error(QKD_ERR_INVALID_ARG, "qkd_adapt_create: position %d given twice", pos);
         emb[pos] = r < p ? -2 - r : -1;
     }
-    std::vector<int32_t> src(n), src_int(n), perm(n), rank(n, -1), rank_int(n);
+    std::vector<int32_t> src(n), src_int(n), rank(n, -1), rank_int(n);
     for (int32_t r = 0; r < p; ++r) rank[punctured[r]] = r;
     int32_t k = 0;
     for (int32_t i = 0; i < n; ++i) {
@@ -229,24 +219,21 @@ static qkd_status adapt_build(qkd_adapt* a, const qkd_code* c, const int32_t* pu
     a->n_payload = n - p - s;
     a->p = p;
     a->s = s;
-    DeviceGuard g(c->device);
-    QKD_HIP(hipMemcpy(perm.data(), c->d_perm, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    // (a code too long for the split kernels has no internal order: the status
+    // the device-to-host copy of its null perm used to give)
+    const std::vector<int32_t>& perm = c->perm;
+    if (perm.size() != (size_t)n)
+        return set_error(QKD_ERR_DEVICE, "qkd_adapt_create: the code has no internal bit order (N=%d)", n);
     for (int32_t q = 0; q < n; ++q) {
-        if (perm[q] < 0 || perm[q] >= n) return set_error(QKD_ERR_BAD_CODE, "qkd_adapt_create: bad bit order");
         src_int[q] = src[perm[q]];
         rank_int[q] = rank[perm[q]];
     }
-    const size_t bytes = (size_t)n * sizeof(int32_t);
-    QKD_HIP(hipMalloc(&a->d_rank_orig, bytes));
-    QKD_HIP(hipMalloc(&a->d_rank_int, bytes));
-    QKD_HIP(hipMemcpy(a->d_rank_orig, rank.data(), bytes, hipMemcpyHostToDevice));
-    QKD_HIP(hipMemcpy(a->d_rank_int, rank_int.data(), bytes, hipMemcpyHostToDevice));
-    QKD_HIP(hipMalloc(&a->d_src_orig, bytes));
-    QKD_HIP(hipMalloc(&a->d_src_int, bytes));
-    QKD_HIP(hipMalloc(&a->d_emb, bytes));
-    QKD_HIP(hipMemcpy(a->d_src_orig, src.data(), bytes, hipMemcpyHostToDevice));
-    QKD_HIP(hipMemcpy(a->d_src_int, src_int.data(), bytes, hipMemcpyHostToDevice));
-    QKD_HIP(hipMemcpy(a->d_emb, emb.data(), bytes, hipMemcpyHostToDevice));
+    DeviceGuard g(c->device);
+    QKD_HIP(a->d_rank_orig.upload(rank));
+    QKD_HIP(a->d_rank_int.upload(rank_int));
+    QKD_HIP(a->d_src_orig.upload(src));
+    QKD_HIP(a->d_src_int.upload(src_int));
+    QKD_HIP(a->d_emb.upload(emb));
     return QKD_OK;
 }
 
@@ -276,7 +263,7 @@ qkd_adapt* qkd_adapt_create(const qkd_code* code, const int32_t* punctured, int3
         a->device = code->device;
         st = adapt_build(a, code, punctured, p, shortened, s);
         if (st != QKD_OK) {
-            adapt_free(a);
+            delete a;
             a = nullptr;
         }
     }
@@ -284,9 +271,7 @@ qkd_adapt* qkd_adapt_create(const qkd_code* code, const int32_t* punctured, int3
     return a;
 }
 
-void qkd_adapt_destroy(qkd_adapt* a) {
-    if (a) adapt_free(a);
-}
+void qkd_adapt_destroy(qkd_adapt* a) { delete a; }
 
 qkd_status qkd_adapt_get_info(const qkd_adapt* a, qkd_adapt_info* info) {
     if (!a || !info) return set_error(QKD_ERR_INVALID_ARG, "null argument");

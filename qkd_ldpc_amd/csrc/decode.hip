@@ -29,6 +29,7 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <memory>
 #include <cstdlib>
 #include <cstring>
 
@@ -1051,7 +1052,7 @@ __global__ __launch_bounds__(kKgBlock) void keygen_split_kernel(const uint64_t* 
     __syncthreads();
 
     if (!shuffle_wave) {
-        // Alice's bits: cb is a multiple of 32 (host.cpp), so a lane's chunk
+        // Alice's bits: cb is a multiple of 32 (qkd_layout.h), so a lane's chunk
         // is whole 32-bit words of the key, written by that lane alone. A
         // block of 32 draws shifts each draw's top bit into a register from
         // the right (one v_alignbit_b32) and reverses it at the end, so draw
@@ -1504,19 +1505,15 @@ static qkd_status decode_grid(const qkd_code* c, DecodeFn fn, size_t lds, int* g
 qkd_status ws_reserve_decode(qkd_workspace* ws, size_t slots) {
     const qkd_code* c = ws->code;
     if (!ws->counter) {
-        QKD_HIP(hipMalloc(&ws->counter, 128));
+        QKD_HIP(ws->counter.alloc(32));
         QKD_HIP(hipMemset(ws->counter, 0, 128));
     }
-    if (ws->c2b_slots >= slots) return QKD_OK;
-    if (ws->c2b) QKD_HIP(hipFree(ws->c2b));
-    ws->c2b = nullptr;
-    ws->c2b_slots = 0;
     // per slot: the c2b store (max_dv rows) and, at the end, a total row
     // (large codes keep their bit totals there)
-    const size_t bytes = slots * ((size_t)c->max_dv + 1) * c->n_pad * sizeof(double);
-    if (hipMalloc(&ws->c2b, bytes) != hipSuccess)
-        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of c2b scratch", bytes);
-    ws->c2b_slots = slots;
+    const size_t elems = slots * ((size_t)c->max_dv + 1) * c->n_pad;
+    if (ws->c2b.reserve(elems) != hipSuccess)
+        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of c2b scratch",
+                         elems * sizeof(double));
     return QKD_OK;
 }
 
@@ -1524,56 +1521,30 @@ qkd_status ws_reserve_keys(qkd_workspace* ws, size_t frames, size_t low_words) {
     const qkd_code* c = ws->code;
     const size_t words = (size_t)(c->n + 63) / 64;
     if (ws->key_frames < frames) {
-        if (ws->alice_w) QKD_HIP(hipFree(ws->alice_w));
-        if (ws->bob_w) QKD_HIP(hipFree(ws->bob_w));
-        if (ws->synw) QKD_HIP(hipFree(ws->synw));
-        if (ws->zout) QKD_HIP(hipFree(ws->zout));
-        ws->alice_w = ws->bob_w = ws->zout = nullptr;
-        ws->synw = nullptr;
         ws->key_frames = 0;
         const size_t syn_words = 2 * (size_t)decode_m_words(c->m);
-        if (hipMalloc(&ws->alice_w, frames * words * 8) != hipSuccess ||
-            hipMalloc(&ws->bob_w, frames * words * 8) != hipSuccess ||
-            hipMalloc(&ws->synw, frames * syn_words * 4) != hipSuccess ||
-            hipMalloc(&ws->zout, frames * words * 8) != hipSuccess)
+        if (ws->alice_w.reserve(frames * words) != hipSuccess || ws->bob_w.reserve(frames * words) != hipSuccess ||
+            ws->synw.reserve(frames * syn_words) != hipSuccess || ws->zout.reserve(frames * words) != hipSuccess)
             return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate keys for %zu frames", frames);
         ws->key_frames = frames;
     }
-    if (ws->low_words < low_words) {
-        if (ws->low) QKD_HIP(hipFree(ws->low));
-        ws->low = nullptr;
-        ws->low_words = 0;
-        if (hipMalloc(&ws->low, low_words * 4) != hipSuccess)
-            return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate shuffle scratch");
-        ws->low_words = low_words;
-    }
+    if (ws->low.reserve(low_words) != hipSuccess)
+        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate shuffle scratch");
     return QKD_OK;
 }
 
-static qkd_status ws_free(qkd_workspace* ws) {
-    DeviceGuard g(ws->device);
-    if (ws->c2b) (void)hipFree(ws->c2b);
-    if (ws->counter) (void)hipFree(ws->counter);
-    if (ws->alice_w) (void)hipFree(ws->alice_w);
-    if (ws->bob_w) (void)hipFree(ws->bob_w);
-    if (ws->synw) (void)hipFree(ws->synw);
-    if (ws->zout) (void)hipFree(ws->zout);
-    if (ws->low) (void)hipFree(ws->low);
-    if (ws->ckpt) (void)hipFree(ws->ckpt);
-    if (ws->win) (void)hipFree(ws->win);
-    if (ws->ilv) (void)hipFree(ws->ilv);
-    if (ws->fb_list) (void)hipFree(ws->fb_list);
-    if (ws->cls) (void)hipFree(ws->cls);
-    if (ws->blind_list) (void)hipFree(ws->blind_list);
-    if (ws->blind_open) (void)hipFree(ws->blind_open);
-    if (ws->vkey) (void)hipFree(ws->vkey);
-    if (ws->spec_stat_ev) (void)hipEventSynchronize(ws->spec_stat_ev);
-    if (ws->spec_stat_host) (void)hipHostFree(ws->spec_stat_host);
-    if (ws->spec_stat_ev) (void)hipEventDestroy(ws->spec_stat_ev);
-    if (ws->done) (void)hipEventDestroy(ws->done);
-    for (hipEvent_t e : ws->dec_ev) (void)hipEventDestroy(e);
-    return QKD_OK;
+}  // namespace qkd
+
+qkd_workspace::~qkd_workspace() {
+    qkd::DeviceGuard g(device);
+    if (spec_stat_ev) (void)hipEventSynchronize(spec_stat_ev);
+    if (spec_stat_host) (void)hipHostFree(spec_stat_host);
+    if (spec_stat_ev) (void)hipEventDestroy(spec_stat_ev);
+    if (done) (void)hipEventDestroy(done);
+    for (hipEvent_t e : dec_ev) (void)hipEventDestroy(e);
 }
+
+namespace qkd {
 
 static std::mutex g_default_ws_mu;
 
@@ -1679,19 +1650,19 @@ static qkd_status plan_for_layout(const qkd_code* c, const SplitLds& L, int dc, 
     const auto key = std::make_pair(L.S, ((uint32_t)cl_form << 28) | ((uint32_t)L.msg << 8) | (uint32_t)dc | (esz == 4 ? 0x80u : 0u));
     auto it = c->d_plan_enc.find(key);
     if (it == c->d_plan_enc.end()) {
-        std::vector<uint2> enc(c->plan_slot_host);
+        std::vector<U2> enc(c->plan_slot);
         for (size_t k = 0; k < enc.size(); ++k) {
-            uint2& w = enc[k];
+            U2& w = enc[k];
             w.x = esz == 4 ? (uint32_t)L.msg + w.x * 4u : encode_slot(w.x, L.S, (uint32_t)L.msg, (uint32_t)sizeof(double));
             w.y = encode_seg(w.y & qkdp::kPlanChkMask, (w.y >> 20) & 63u, (w.y >> 26) + 1, (uint32_t)(k & 63),
                              (uint32_t)dc);
         }
         if (cl_form != 0) {
-            const qkd_code::ClHost& h = c->cl_host[cl_form - 1];
+            const ClHost& h = c->cl_host[cl_form - 1];
             const size_t at = enc.size();
             enc.insert(enc.end(), h.rem.begin(), h.rem.end());
             for (size_t k = at; k < enc.size(); ++k) {
-                uint2& w = enc[k];
+                U2& w = enc[k];
                 w.x = encode_slot(w.x, L.S, (uint32_t)L.msg, (uint32_t)sizeof(double));
                 w.y = encode_seg(w.y & qkdp::kPlanChkMask, (w.y >> 20) & 63u, (w.y >> 26) + 1, (uint32_t)(k & 63),
                                  (uint32_t)dc);
@@ -1717,17 +1688,15 @@ static qkd_status plan_for_layout(const qkd_code* c, const SplitLds& L, int dc, 
                 for (size_t l = 0; l < 64; ++l) words[(t * (size_t)(dc + 1) + (size_t)dc) * 64 + l] = h.chk[t * 64 + l];
             }
             words.resize((words.size() + 1) & ~(size_t)1, 0u);
-            for (size_t k = 0; k < words.size(); k += 2) enc.push_back(make_uint2(words[k], words[k + 1]));
+            for (size_t k = 0; k < words.size(); k += 2) enc.push_back(U2{words[k], words[k + 1]});
         }
-        uint2* d = nullptr;
-        if (hipMalloc(&d, enc.size() * sizeof(uint2)) != hipSuccess)
+        DevBuf<uint2> d;
+        if (d.alloc(enc.size()) != hipSuccess)
             return set_error(QKD_ERR_OUT_OF_MEMORY, "code: cannot allocate %zu B for an encoded plan",
                              enc.size() * sizeof(uint2));
-        if (hipMemcpy(d, enc.data(), enc.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
+        if (hipMemcpy(d, enc.data(), enc.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess)
             return set_error(QKD_ERR_DEVICE, "code: encoded plan upload failed");
-        }
-        it = c->d_plan_enc.emplace(key, d).first;
+        it = c->d_plan_enc.emplace(key, std::move(d)).first;
     }
     *out = it->second;
     return QKD_OK;
@@ -1870,7 +1839,7 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
             if (const DbgOpt g = debug_option(ws, "QKD_DECODE_GRID")) grid = std::max(1, std::min(grid, g.as_int()));
             s = ws_reserve_decode(ws, (size_t)grid);
             if (s != QKD_OK) return s;
-            a.code = c->view_split();     // the internal bit order (host.cpp build_code)
+            a.code = c->view_split();     // the internal bit order (qkd_layout.h)
             a.c2b = ws->c2b;
             a.plan_enc = nullptr;
             a.cl_split = 0;
@@ -1891,7 +1860,7 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
                 if (s != QKD_OK) return s;
                 a.cl_split = 0;
                 if (cl_form != 0) {
-                    const qkd_code::ClHost& h = c->cl_host[cl_form - 1];
+                    const ClHost& h = c->cl_host[cl_form - 1];
                     a.cl_split = 0x80000000u | (uint32_t)h.cl_tasks | ((uint32_t)h.rem_tasks << 16);
                     ws->last_cl_form = cl_form;
                     ws->last_cl_tasks = h.cl_tasks;
@@ -1927,11 +1896,11 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
             const bool timing = (bool)debug_option(ws, "QKD_PHASE_TIMING");
             a.phase = nullptr;
             if (timing) {
-                a.phase = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws->counter) + 64);
+                a.phase = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws->counter.get()) + 64);
                 QKD_HIP(hipMemsetAsync(a.phase, 0, 64, stream));
             }
             a.replay_count = ws->counter + 1;
-            a.spec_replays = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws->counter) + 120);
+            a.spec_replays = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws->counter.get()) + 120);
             if (spec) {
                 // (a long code: the interleaved decoder speculates; no split speculation)
                 if (!long_code) {
@@ -1947,15 +1916,9 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
                 if (ckpt && !long_code) {
                     // one saved message store per resident workgroup
                     const size_t need = (size_t)grid * slots;
-                    if (ws->ckpt_slots < need) {
-                        if (ws->ckpt) QKD_HIP(hipFree(ws->ckpt));
-                        ws->ckpt = nullptr;
-                        ws->ckpt_slots = 0;
-                        if (hipMalloc(&ws->ckpt, need * sizeof(double)) != hipSuccess)
-                            return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of checkpoints",
-                                             need * sizeof(double));
-                        ws->ckpt_slots = need;
-                    }
+                    if (ws->ckpt.reserve(need) != hipSuccess)
+                        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of checkpoints",
+                                         need * sizeof(double));
                     a.ckpt = ws->ckpt;
                     a.ckpt_stride = (uint32_t)slots;
                 }
@@ -1968,14 +1931,8 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
                 a.win_lag = kSpecWinLag;
                 a.win_count = (uint32_t)((a.n_frames + (1u << kSpecWinShift) - 1) >> kSpecWinShift);
                 const size_t need = 2 * (size_t)a.win_count;
-                if (ws->win_words < need) {
-                    if (ws->win) QKD_HIP(hipFree(ws->win));
-                    ws->win = nullptr;
-                    ws->win_words = 0;
-                    if (hipMalloc(&ws->win, need * sizeof(uint32_t)) != hipSuccess)
-                        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the policy windows");
-                    ws->win_words = need;
-                }
+                if (ws->win.reserve(need) != hipSuccess)
+                    return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the policy windows");
                 a.win = ws->win;
             }
             if (rule == kRuleSp64 || msr) {
@@ -2022,22 +1979,15 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
                 // (QKD_ILV_GRID caps the workgroups: tests take columns through several frames)
                 if (const DbgOpt g = debug_option(ws, "QKD_ILV_GRID")) igrid = std::max(1, std::min(igrid, g.as_int()));
                 const size_t need = (size_t)igrid * istride;
-                if (ws->ilv_elems < need) {
-                    if (ws->ilv) QKD_HIP(hipFree(ws->ilv));
-                    ws->ilv = nullptr;
-                    ws->ilv_elems = 0;
-                    if (hipMalloc(&ws->ilv, need * sizeof(double)) != hipSuccess) {
-                        // (one message region per resident workgroup: ~6 GB at N
-                        // = 60,000. Unless forced, the split kernel, which needs
-                        // far less, decodes the batch instead)
-                        (void)hipGetLastError();
-                        if (ilv_forced)
-                            return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of "
-                                                                    "interleaved message lines", need * sizeof(double));
-                        ilv = false;
-                    } else {
-                        ws->ilv_elems = need;
-                    }
+                if (ws->ilv.reserve(need) != hipSuccess) {
+                    // (one message region per resident workgroup: ~6 GB at N
+                    // = 60,000. Unless forced, the split kernel, which needs
+                    // far less, decodes the batch instead)
+                    (void)hipGetLastError();
+                    if (ilv_forced)
+                        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of "
+                                                                "interleaved message lines", need * sizeof(double));
+                    ilv = false;
                 }
             }
             // (a long code the interleaved decoder does not take: the classic kernel)
@@ -2045,16 +1995,8 @@ static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs
                 a = a_in;
                 goto classic_path;
             }
-            if (ilv) {
-                if (ws->fb_frames < a.n_frames) {
-                    if (ws->fb_list) QKD_HIP(hipFree(ws->fb_list));
-                    ws->fb_list = nullptr;
-                    ws->fb_frames = 0;
-                    if (hipMalloc(&ws->fb_list, (size_t)a.n_frames * sizeof(uint32_t)) != hipSuccess)
-                        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the hand-off list");
-                    ws->fb_frames = a.n_frames;
-                }
-            }
+            if (ilv && ws->fb_list.reserve(a.n_frames) != hipSuccess)
+                return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the hand-off list");
             // [0] frame queue, [1] replays: zeroed by frame_syn_kernel on the
             // keys path (it runs first on this stream: block 0 writes both
             // words), by a memset otherwise -- one branch, so a keys-mode
@@ -2139,14 +2081,14 @@ classic_path:
     a.c2b = ws->c2b;
     a.c2b_stride = (size_t)c->max_dv * c->n_pad;
     // the workspace holds one total row per slot after all the message stores
-    a.totals = gt ? ws->c2b + ws->c2b_slots * a.c2b_stride : nullptr;
+    a.totals = gt ? ws->c2b + ws->c2b.size() / ((size_t)c->max_dv + 1) * (size_t)c->max_dv : nullptr;
     a.totals_stride = c->n_pad;
     a.counter = ws->counter;
     QKD_HIP(hipMemsetAsync(ws->counter, 0, 4, stream));
     const bool timing = (bool)debug_option(ws, "QKD_PHASE_TIMING");
     a.phase = nullptr;
     if (timing) {
-        a.phase = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws->counter) + 64);
+        a.phase = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws->counter.get()) + 64);
         QKD_HIP(hipMemsetAsync(a.phase, 0, 64, stream));
     }
     QKD_HIP(decoder_event(ws, stream));
@@ -2210,7 +2152,6 @@ qkd_workspace* qkd_workspace_create(const qkd_code* code, qkd_status* status) {
 
 void qkd_workspace_destroy(qkd_workspace* ws) {
     if (!ws) return;
-    ws_free(ws);
     delete ws;
 }
 
@@ -2446,13 +2387,8 @@ qkd_status qkd_reconcile_batch(const qkd_code* c, qkd_workspace* ws, const uint8
 // one class byte per bit and frame: the only per-bit input the class-mode decoder reads
 static qkd_status ws_reserve_classes(qkd_workspace* ws, size_t n_frames) {
     const size_t need = n_frames * (size_t)ws->code->n;
-    if (ws->cls_bytes >= need) return QKD_OK;
-    if (ws->cls) QKD_HIP(hipFree(ws->cls));
-    ws->cls = nullptr;
-    ws->cls_bytes = 0;
-    if (hipMalloc(&ws->cls, need) != hipSuccess)
+    if (ws->cls.reserve(need) != hipSuccess)
         return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of class bytes", need);
-    ws->cls_bytes = need;
     return QKD_OK;
 }
 
@@ -2503,14 +2439,8 @@ static qkd_status class_verify_key(qkd_workspace* ws, const qkd_adapt* ad, const
         return QKD_OK;
     }
     const size_t words = qkdv::verify_key_words(ad->n_payload);
-    if (ws->vkey_words < words) {
-        if (ws->vkey) QKD_HIP(hipFree(ws->vkey));
-        ws->vkey = nullptr;
-        ws->vkey_words = 0;
-        if (hipMalloc(&ws->vkey, words * sizeof(uint64_t)) != hipSuccess)
-            return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the verification key string");
-        ws->vkey_words = words;
-    }
+    if (ws->vkey.reserve(words) != hipSuccess)
+        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the verification key string");
     QKD_HIP(launch_verify_expand(cv.seed, (uint32_t)words, ws->vkey, stream));
     *key = ws->vkey;
     return QKD_OK;
@@ -2620,13 +2550,8 @@ static qkd_status blind_run(const char* entry, const qkd_code* c, qkd_workspace*
     s = ws_reserve_decode(ws, 0);             // (the counter words)
     if (s != QKD_OK) return s;
     if (ws->blind_frames < n_frames) {
-        if (ws->blind_list) QKD_HIP(hipFree(ws->blind_list));
-        if (ws->blind_open) QKD_HIP(hipFree(ws->blind_open));
-        ws->blind_list = nullptr;
-        ws->blind_open = nullptr;
         ws->blind_frames = 0;
-        if (hipMalloc(&ws->blind_list, n_frames * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc(&ws->blind_open, n_frames) != hipSuccess)
+        if (ws->blind_list.reserve(n_frames) != hipSuccess || ws->blind_open.reserve(n_frames) != hipSuccess)
             return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the open-frame list");
         ws->blind_frames = n_frames;
     }
@@ -2899,23 +2824,17 @@ qkd_status qkd_interactive_batch(const qkd_code* c, qkd_workspace* ws, uint64_t 
         s = ws_reserve_keys(ws, 1, 1);
         if (s != QKD_OK) return s;
         const uint32_t words = (uint32_t)((c->n + 63) / 64);
-        uint64_t *d_a = nullptr, *d_b = nullptr;
-        uint32_t *d_ne = nullptr, *d_low = nullptr, *d_it = nullptr;
-        uint8_t* d_flags = nullptr;
-        auto cleanup = [&]() {
-            for (void* q : {(void*)d_a, (void*)d_b, (void*)d_ne, (void*)d_low, (void*)d_it, (void*)d_flags})
-                if (q) (void)hipFree(q);
-        };
-        if (hipMalloc(&d_a, run * words * 8) != hipSuccess || hipMalloc(&d_b, run * words * 8) != hipSuccess ||
-            hipMalloc(&d_ne, run * 4) != hipSuccess || hipMalloc(&d_low, (size_t)max_ne * 4) != hipSuccess ||
-            hipMalloc(&d_it, run * 4) != hipSuccess || hipMalloc(&d_flags, run * 2) != hipSuccess) {
-            cleanup();
+        DevBuf<uint64_t> d_a, d_b;
+        DevBuf<uint32_t> d_ne, d_low, d_it;
+        DevBuf<uint8_t> d_flags;
+        if (d_a.alloc(run * words) != hipSuccess || d_b.alloc(run * words) != hipSuccess ||
+            d_ne.alloc(run) != hipSuccess || d_low.alloc(max_ne) != hipSuccess || d_it.alloc(run) != hipSuccess ||
+            d_flags.alloc(run * 2) != hipSuccess)
             return set_error(QKD_ERR_OUT_OF_MEMORY, "interactive: cannot allocate");
-        }
         hipError_t e = hipMemcpy(d_ne, ne.data(), run * 4, hipMemcpyHostToDevice);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(keygen_stream_kernel, dim3(1), dim3(64), 0, st, simulation_seed, (uint32_t)c->n, words,
-                               (uint32_t)run, d_ne, d_a, d_b, d_low);
+                               (uint32_t)run, d_ne.get(), d_a.get(), d_b.get(), d_low.get());
             e = hipGetLastError();
         }
         for (size_t p = 0; p < run && e == hipSuccess && s == QKD_OK; ++p) {
@@ -2930,7 +2849,6 @@ qkd_status qkd_interactive_batch(const qkd_code* c, qkd_workspace* ws, uint64_t 
         if (e == hipSuccess && s == QKD_OK) e = hipMemcpy(iterations, d_it, run * 4, hipMemcpyDeviceToHost);
         if (e == hipSuccess && s == QKD_OK) e = hipMemcpy(syndromes_match, d_flags, run, hipMemcpyDeviceToHost);
         if (e == hipSuccess && s == QKD_OK) e = hipMemcpy(keys_match, d_flags + run, run, hipMemcpyDeviceToHost);
-        cleanup();
         if (s != QKD_OK) return s;
         if (e != hipSuccess) return set_error(QKD_ERR_DEVICE, "interactive: %s", hipGetErrorString(e));
     }
@@ -3131,26 +3049,21 @@ qkd_status qkd_debug_phi_sweep(int which, uint32_t first_bits, uint32_t last_bit
     clear_error();
     if ((which != 4 && which != 5) || !result || first_bits > last_bits || last_bits >= 0x7f800000u)
         return set_error(QKD_ERR_INVALID_ARG, "bad argument");
-    unsigned long long* d_cnt = nullptr;
-    uint32_t* d_mx = nullptr;
-    QKD_HIP(hipMalloc(&d_cnt, 4 * sizeof(unsigned long long)));
-    if (hipMalloc(&d_mx, 4 * sizeof(uint32_t)) != hipSuccess) {
-        (void)hipFree(d_cnt);
-        return set_error(QKD_ERR_OUT_OF_MEMORY, "phi sweep: cannot allocate");
-    }
+    DevBuf<unsigned long long> d_cnt;
+    DevBuf<uint32_t> d_mx;
+    QKD_HIP(d_cnt.alloc(4));
+    if (d_mx.alloc(4) != hipSuccess) return set_error(QKD_ERR_OUT_OF_MEMORY, "phi sweep: cannot allocate");
     hipError_t e = hipMemset(d_cnt, 0, 4 * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(d_mx, 0, 4 * sizeof(uint32_t));
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(phi_sweep_kernel, dim3(4096), dim3(256), 0, nullptr, which, first_bits, last_bits, d_cnt,
-                           d_mx);
+        hipLaunchKernelGGL(phi_sweep_kernel, dim3(4096), dim3(256), 0, nullptr, which, first_bits, last_bits, d_cnt.get(),
+                           d_mx.get());
         e = hipGetLastError();
     }
     unsigned long long cnt[4] = {0, 0, 0, 0};
     uint32_t mx[4] = {0, 0, 0, 0};
     if (e == hipSuccess) e = hipMemcpy(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(mx, d_mx, sizeof mx, hipMemcpyDeviceToHost);
-    (void)hipFree(d_cnt);
-    (void)hipFree(d_mx);
     if (e != hipSuccess) return set_error(QKD_ERR_DEVICE, "phi sweep: %s", hipGetErrorString(e));
     for (int k = 0; k < 4; ++k) result[k] = cnt[k];
     for (int k = 0; k < 4; ++k) result[4 + k] = mx[k];
@@ -3172,29 +3085,20 @@ qkd_status qkd_trace_decode(const qkd_code* c, const double* llr, const uint8_t*
     qkd_workspace* ws = qkd_workspace_create(c, &s);
     if (!ws) return s;
     const size_t stride = (size_t)c->max_dv * c->n_pad + c->n_pad;
-    double *d_llr = nullptr, *d_tr = nullptr;
-    uint8_t *d_syn = nullptr, *d_ok = nullptr;
-    uint32_t* d_it = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : {(void*)d_llr, (void*)d_tr, (void*)d_syn, (void*)d_ok, (void*)d_it})
-            if (p) (void)hipFree(p);
-        qkd_workspace_destroy(ws);
-    };
+    const std::unique_ptr<qkd_workspace> ws_owner(ws);
+    DevBuf<double> d_llr, d_tr;
+    DevBuf<uint8_t> d_syn, d_ok;
+    DevBuf<uint32_t> d_it;
     hipStream_t st = nullptr;
-    if (hipMalloc(&d_llr, (size_t)c->n * 8) != hipSuccess || hipMalloc(&d_syn, (size_t)c->m) != hipSuccess ||
-        hipMalloc(&d_ok, 1) != hipSuccess || hipMalloc(&d_it, 4) != hipSuccess ||
-        hipMalloc(&d_tr, stride * max_iterations * 8) != hipSuccess) {
-        cleanup();
+    if (d_llr.alloc((size_t)c->n) != hipSuccess || d_syn.alloc((size_t)c->m) != hipSuccess ||
+        d_ok.alloc(1) != hipSuccess || d_it.alloc(1) != hipSuccess ||
+        d_tr.alloc(stride * max_iterations) != hipSuccess)
         return set_error(QKD_ERR_OUT_OF_MEMORY, "trace: cannot allocate %zu B", stride * max_iterations * 8);
-    }
     std::vector<uint8_t> syn01((size_t)c->m);
     for (int32_t j = 0; j < c->m; ++j) syn01[j] = syndrome[j] ? 1 : 0;
     hipError_t e = hipMemcpy(d_llr, llr, (size_t)c->n * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_syn, syn01.data(), (size_t)c->m, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        cleanup();
-        return set_error(QKD_ERR_DEVICE, "trace: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return set_error(QKD_ERR_DEVICE, "trace: %s", hipGetErrorString(e));
     DecodeArgs a{};
     a.pinf = std::numeric_limits<float>::infinity();
     a.n_frames = 1;
@@ -3230,7 +3134,6 @@ qkd_status qkd_trace_decode(const qkd_code* c, const double* llr, const uint8_t*
             }
         }
     }
-    cleanup();
     return s;
 }
 
@@ -3240,7 +3143,7 @@ qkd_status qkd_debug_spec_replays(qkd_workspace* ws, uint64_t* replays, int rese
     if (!ws->counter) return QKD_OK;
     DeviceGuard g(ws->device);
     QKD_HIP(hipDeviceSynchronize());
-    char* p = reinterpret_cast<char*>(ws->counter) + 120;
+    char* p = reinterpret_cast<char*>(ws->counter.get()) + 120;
     QKD_HIP(hipMemcpy(replays, p, 8, hipMemcpyDeviceToHost));
     if (reset) QKD_HIP(hipMemset(p, 0, 8));
     return QKD_OK;
@@ -3273,7 +3176,7 @@ qkd_status qkd_debug_phase_cycles(qkd_workspace* ws, uint64_t* cycles7) {
     if (!ws->counter) return set_error(QKD_ERR_INVALID_ARG, "workspace has not decoded yet");
     DeviceGuard g(ws->device);
     QKD_HIP(hipDeviceSynchronize());
-    QKD_HIP(hipMemcpy(cycles7, reinterpret_cast<char*>(ws->counter) + 64, 56, hipMemcpyDeviceToHost));
+    QKD_HIP(hipMemcpy(cycles7, reinterpret_cast<char*>(ws->counter.get()) + 64, 56, hipMemcpyDeviceToHost));
     return QKD_OK;
 }
 

@@ -1,6 +1,6 @@
 """LDS bank model of the split decoder's check phases (CPU, no GPU): for the
 N=10240 code, the wave plan (a port of qkd_plan.h build_wave_plan), the internal
-bit order (host.cpp build_code) and an LDS slot budget S, count per task and
+bit order (qkd_layout.h internal_bit_order) and an LDS slot budget S, count per task and
 half-wave the LDS slot accesses (x = row * n_pad + bit < S) that share a bank pair
 (x mod 32, 8-byte slots over 64 four-byte banks) with a different slot: the extra
 cycles a ds_read_b64 / ds_write_b64 of that half-wave costs. Also the number of
