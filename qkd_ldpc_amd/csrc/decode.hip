@@ -1371,135 +1371,82 @@ __global__ __launch_bounds__(64) void counters_merge_kernel(const qkd_counters* 
 // ---- launch plumbing --------------------------------------------------------
 
 
-// Check-degree buckets: the in-check product reads DC values per lane.
-template <int MODE, int RULE, bool CLAMP, bool GT>
-static DecodeFn pick_decode_dc(int max_dc, int* dc) {
-    if constexpr (GT) {                           // large codes: two buckets
-        if (max_dc <= 16) { *dc = 16; return decode_kernel<MODE, RULE, 16, CLAMP, true>; }
-        *dc = 64;
-        return decode_kernel<MODE, RULE, 64, CLAMP, true>;
-    } else {
-        if (max_dc <= 4) { *dc = 4; return decode_kernel<MODE, RULE, 4, CLAMP, false>; }
-        if (max_dc <= 6) { *dc = 6; return decode_kernel<MODE, RULE, 6, CLAMP, false>; }
-        if (max_dc <= 8) { *dc = 8; return decode_kernel<MODE, RULE, 8, CLAMP, false>; }
-        if (max_dc <= 16) { *dc = 16; return decode_kernel<MODE, RULE, 16, CLAMP, false>; }
-        if constexpr (RULE == kRuleMinSumLds || RULE == kRuleMinSumLdsSc) {   // decode_ms_fits: degree <= 32
-            *dc = 32;
-            return decode_kernel<MODE, RULE, 32, CLAMP, false>;
-        } else {
-            *dc = 64;
-            return decode_kernel<MODE, RULE, 64, CLAMP, false>;
-        }
-    }
-}
-
-template <int MODE, int RULE, bool GT>
-static DecodeFn pick_decode_clamp(bool clamp, int max_dc, int* dc) {
-    return clamp ? pick_decode_dc<MODE, RULE, true, GT>(max_dc, dc)
-                 : pick_decode_dc<MODE, RULE, false, GT>(max_dc, dc);
-}
-
-template <int MODE, bool GT>
-static DecodeFn pick_decode_rule(int rule, bool clamp, int max_dc, int* dc) {
-    if (rule == kRuleSp32) return pick_decode_clamp<MODE, kRuleSp32, GT>(clamp, max_dc, dc);
-    if (rule == kRuleMinSum) return pick_decode_clamp<MODE, kRuleMinSum, GT>(clamp, max_dc, dc);
-    if constexpr (!GT)
-        if (rule == kRuleMinSumLds) return pick_decode_clamp<MODE, kRuleMinSumLds, false>(clamp, max_dc, dc);
-    if constexpr (!GT)
-        if (rule == kRuleMinSumLdsSc) return pick_decode_clamp<MODE, kRuleMinSumLdsSc, false>(clamp, max_dc, dc);
-    return pick_decode_clamp<MODE, kRuleSp64, GT>(clamp, max_dc, dc);
-}
-
-// the erasure rule's kernels (binary64): the LLR path with QKD_FLAG_ERASURES
-// and the class-byte path
-template <int MODE, bool CLAMP, bool GT, bool VFY = false>
-static DecodeFn pick_decode_era_dc(int max_dc, int* dc) {
+// The instantiations of decode_kernel, by key (qkd_launch.h KernelKey).
+// Buckets: 4 / 6 / 8 / 16 / 64; the LDS-state min-sum rules end at 32 (sign
+// bits in one word) and have no large-code form; the large-code kernels (GT)
+// 16 / 64. (The compiler emits the kernels in the order these functions name
+// them.)
+template <int MODE, int RULE, bool CLAMP, bool GT, bool ERA, bool VFY>
+static DecodeFn classic_bucket(int dc) {
     if constexpr (!GT) {
-        if (max_dc <= 4) { *dc = 4; return decode_kernel<MODE, kRuleSp64, 4, CLAMP, false, true, VFY>; }
-        if (max_dc <= 6) { *dc = 6; return decode_kernel<MODE, kRuleSp64, 6, CLAMP, false, true, VFY>; }
-        if (max_dc <= 8) { *dc = 8; return decode_kernel<MODE, kRuleSp64, 8, CLAMP, false, true, VFY>; }
+        if (dc == 4) return decode_kernel<MODE, RULE, 4, CLAMP, false, ERA, VFY>;
+        if (dc == 6) return decode_kernel<MODE, RULE, 6, CLAMP, false, ERA, VFY>;
+        if (dc == 8) return decode_kernel<MODE, RULE, 8, CLAMP, false, ERA, VFY>;
     }
-    if (max_dc <= 16) { *dc = 16; return decode_kernel<MODE, kRuleSp64, 16, CLAMP, GT, true, VFY>; }
-    *dc = 64;
-    return decode_kernel<MODE, kRuleSp64, 64, CLAMP, GT, true, VFY>;
-}
-template <int MODE, bool VFY = false>
-static DecodeFn pick_decode_era(bool clamp, int max_dc, bool gt, int* dc) {
-    if (gt)
-        return clamp ? pick_decode_era_dc<MODE, true, true, VFY>(max_dc, dc)
-                     : pick_decode_era_dc<MODE, false, true, VFY>(max_dc, dc);
-    return clamp ? pick_decode_era_dc<MODE, true, false, VFY>(max_dc, dc)
-                 : pick_decode_era_dc<MODE, false, false, VFY>(max_dc, dc);
-}
-
-// vfy (kModeClass): the instantiations that take the payload's tag (DecodeArgs::vkey)
-static DecodeFn pick_decode(int mode, int rule, bool clamp, int max_dc, bool gt, int* dc, bool era = false,
-                            bool vfy = false) {
-    if (era || mode == kModeClass) {
-        if (rule != kRuleSp64 || mode == kModeKeys) return nullptr;
-        if (mode == kModeClass && vfy) return pick_decode_era<kModeClass, true>(clamp, max_dc, gt, dc);
-        return mode == kModeClass ? pick_decode_era<kModeClass>(clamp, max_dc, gt, dc)
-                                  : pick_decode_era<kModeLlr>(clamp, max_dc, gt, dc);
+    if (dc == 16) return decode_kernel<MODE, RULE, 16, CLAMP, GT, ERA, VFY>;
+    if constexpr (RULE == kRuleMinSumLds || RULE == kRuleMinSumLdsSc) {
+        if (dc == 32) return decode_kernel<MODE, RULE, 32, CLAMP, GT, ERA, VFY>;
+    } else {
+        if (dc == 64) return decode_kernel<MODE, RULE, 64, CLAMP, GT, ERA, VFY>;
     }
-    if (gt)
-        return mode == kModeLlr ? pick_decode_rule<kModeLlr, true>(rule, clamp, max_dc, dc)
-                                : pick_decode_rule<kModeKeys, true>(rule, clamp, max_dc, dc);
-    return mode == kModeLlr ? pick_decode_rule<kModeLlr, false>(rule, clamp, max_dc, dc)
-                            : pick_decode_rule<kModeKeys, false>(rule, clamp, max_dc, dc);
+    return nullptr;
 }
-
-static int rule_of(uint32_t flags) {
-    switch (flags & QKD_VARIANT_MASK) {
-        case QKD_VARIANT_SP_F32: return kRuleSp32;
-        case QKD_VARIANT_MINSUM: return kRuleMinSum;
-        default: return kRuleSp64;
+template <int MODE, int RULE, bool GT, bool ERA = false, bool VFY = false>
+static DecodeFn classic_clamp(const KernelKey& k) {
+    return k.clamp ? classic_bucket<MODE, RULE, true, GT, ERA, VFY>(k.dc)
+                   : classic_bucket<MODE, RULE, false, GT, ERA, VFY>(k.dc);
+}
+template <int MODE, bool GT>
+static DecodeFn classic_rule(const KernelKey& k) {
+    switch (k.rule) {
+        case kRuleSp32: return classic_clamp<MODE, kRuleSp32, GT>(k);
+        case kRuleMinSum: return classic_clamp<MODE, kRuleMinSum, GT>(k);
+        case kRuleMinSumLds:
+            if constexpr (!GT) return classic_clamp<MODE, kRuleMinSumLds, false>(k);
+            break;
+        case kRuleMinSumLdsSc:
+            if constexpr (!GT) return classic_clamp<MODE, kRuleMinSumLdsSc, false>(k);
+            break;
+        case kRuleSp64: return classic_clamp<MODE, kRuleSp64, GT>(k);
     }
+    return nullptr;
+}
+// the erasure rule's kernels (binary64): the LLR path with QKD_FLAG_ERASURES
+// and the class-byte path (always; VFY: the instantiations that take the
+// payload's tag, DecodeArgs::vkey)
+template <int MODE, bool VFY>
+static DecodeFn classic_era(const KernelKey& k) {
+    return k.gt ? classic_clamp<MODE, kRuleSp64, true, true, VFY>(k) : classic_clamp<MODE, kRuleSp64, false, true, VFY>(k);
 }
 
-static float minsum_scale_of(uint32_t flags) {
-    const uint32_t q = (flags >> QKD_MINSUM_SCALE_SHIFT) & 0xffu;
-    return q ? (float)q / 256.0f : (float)QKD_MINSUM_DEFAULT_SCALE;
+static DecodeFn classic_kernel(const KernelKey& k) {
+    if (k.kind != kKernelClassic || k.spec || k.lng) return nullptr;
+    if (k.era || k.mode == kModeClass) {
+        if (!k.era || k.rule != kRuleSp64) return nullptr;
+        if (k.mode == kModeClass) return k.vfy ? classic_era<kModeClass, true>(k) : classic_era<kModeClass, false>(k);
+        return k.mode == kModeLlr && !k.vfy ? classic_era<kModeLlr, false>(k) : nullptr;
+    }
+    if (k.vfy || (k.mode != kModeLlr && k.mode != kModeKeys)) return nullptr;
+    if (k.gt) return k.mode == kModeLlr ? classic_rule<kModeLlr, true>(k) : classic_rule<kModeKeys, true>(k);
+    return k.mode == kModeLlr ? classic_rule<kModeLlr, false>(k) : classic_rule<kModeKeys, false>(k);
 }
 
-static size_t decode_lds_bytes(const qkd_code* c, int dc, int tab2_entries, int rule, bool gt = false,
-                               bool sc = false) {
-    const int esz = rule == kRuleSp64 ? 8 : 4;
-    const bool msl = rule == kRuleMinSumLds || rule == kRuleMinSumLdsSc;
-    return DecodeLds(c->n_pad, (c->n + 63) / 64, c->m, dc, tab2_entries, gt ? 0 : esz,
-                     msl ? c->m : 0, esz, msl && sc).bytes;
-}
-
-static constexpr size_t kLdsBytesMax = 160 * 1024;
-// the split decoders' encoded slot words (qkd_decode.h encode_slot): a global
-// slot's word, kSlotGlobalBase + offset, must be an LDS address past any
-// allocation (its LDS access then reads 0 and drops the store)
-static_assert(kLdsBytesMax <= kSlotGlobalBase, "global slot words must lie past the LDS");
-
-static int dc_bucket(int max_dc) {
-    return max_dc <= 4 ? 4 : max_dc <= 6 ? 6 : max_dc <= 8 ? 8 : max_dc <= 16 ? 16 : 64;
-}
-
-// Totals in LDS unless the code is too long for them (the large-code kernels).
-static bool decode_needs_gt(const qkd_code* c, int rule, int tab2_entries) {
-    return c->n > kMaxBitsLds || decode_lds_bytes(c, dc_bucket(c->max_dc), tab2_entries, rule) > kLdsBytesMax;
-}
-
-// The LDS-resident min-sum needs the check state (sign bits in one word:
-// degree <= 32) and all of its LDS in one workgroup.
-static bool decode_ms_fits(const qkd_code* c, bool sc) {
-    if (c->max_dc > 32 || c->n > kMaxBitsLds) return false;
-    const int dc = c->max_dc <= 4 ? 4 : c->max_dc <= 6 ? 6 : c->max_dc <= 8 ? 8 : c->max_dc <= 16 ? 16 : 32;
-    return decode_lds_bytes(c, dc, 0, kRuleMinSumLds, false, sc) <= kLdsBytesMax;
-}
-
-// Resident workgroups of decode_kernel for this code on its device.
-static qkd_status decode_grid(const qkd_code* c, DecodeFn fn, size_t lds, int* grid) {
+// Workgroups of `block` threads and `lds` bytes of fn that can be resident on
+// the code's device (0: none). (The attribute on every launch, for the current
+// device: no process-wide flag to race on or to skip for a second device.)
+static qkd_status resident_grid(const qkd_code* c, DecodeFn fn, int block, size_t lds, int* grid) {
     QKD_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = 0;
-    QKD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, kDecodeBlock, lds));
-    if (per_cu < 1) return set_error(QKD_ERR_UNSUPPORTED, "decode kernel cannot be resident (LDS %zu B)", lds);
+    QKD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, block, lds));
     *grid = per_cu * c->cu_count;
     return QKD_OK;
+}
+// ... of decode_kernel or decode_split_kernel, which must have one
+static qkd_status decode_grid(const qkd_code* c, DecodeFn fn, size_t lds, int* grid) {
+    const qkd_status s = resident_grid(c, fn, kDecodeBlock, lds, grid);
+    if (s == QKD_OK && *grid < 1)
+        return set_error(QKD_ERR_UNSUPPORTED, "decode kernel cannot be resident (LDS %zu B)", lds);
+    return s;
 }
 
 qkd_status ws_reserve_decode(qkd_workspace* ws, size_t slots) {
@@ -1670,7 +1617,7 @@ static qkd_status plan_for_layout(const qkd_code* c, const SplitLds& L, int dc, 
             // per task dc rows of slot words, then the row of check words;
             // entries past a check's degree as the reserved dead word, which
             // must be out of range for this layout's LDS and for the largest
-            // region of global slots a launch gives it (launch_decode: the
+            // region of global slots a launch gives it (choose_decode: the
             // rest rounded up to an odd multiple of kC2bPad, or padded by at
             // most n_pad)
             const size_t slots = (size_t)c->max_dv * c->n_pad;
@@ -1721,383 +1668,307 @@ static qkd_status check_no_static_lds(DecodeFn fn) {
     return QKD_OK;
 }
 
+// What a decode launch writes besides the decoder's own outputs.
 // corrected (qkd_reconcile_batch, or nullptr): popcount(bits_out ^ bob) per
 // frame, from the kernel that follows the decoder. verify
 // (qkd_reconcile_verify_batch, or nullptr): the frames' verification tags, from
 // that kernel too.
 // adapt (kModeClass, qkd_reconcile_adaptive_batch): the plan and Bob's payload;
-// the class bytes are written here, in the bit order of the kernel that runs.
-static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs& a, int mode,
-                                uint32_t flags, hipStream_t stream, uint32_t* corrected = nullptr,
-                                const VerifyArgs* verify = nullptr, const ClassArgs* adapt = nullptr) {
-    int dc = 0;
-    int rule = rule_of(flags);
-    // QKD_FLAG_ERASURES: the binary64 rule's erasure-aware instantiations,
-    // exact iterations only (the interval forms are not defined at t = 0), so
-    // the outputs cannot depend on QKD_SPEC_CAP. A dispatch without such an
-    // instantiation fails below; none applies the reference rule instead.
-    const bool era = (flags & QKD_FLAG_ERASURES) != 0 || mode == kModeClass;
-    if (era) {
-        if (rule != kRuleSp64 || mode == kModeKeys || a.trace || (mode == kModeClass && !adapt))
-            return set_error(QKD_ERR_UNSUPPORTED, "the erasure rule: binary64 variant, LLR or class entry, no trace");
-        a.spec_cap = 0;
-    }
-    // kModeClass: the class bytes of this launch, in the view's bit order
-    auto classes = [&](bool internal) -> hipError_t {
-        if (mode != kModeClass) return hipSuccess;
-        a.src = internal ? adapt->src_int : adapt->src_orig;
-        a.cls = adapt->cls;
-        // (a round of qkd_reconcile_blind_batch: the frames of its list only)
-        if (adapt->blind)
-            return launch_blind_classes(a.src, internal ? adapt->blind->rank_int : adapt->blind->rank_orig,
-                                        adapt->bob_payload, *adapt->blind, (uint32_t)c->n, a.n_payload, a.n_frames,
-                                        adapt->cls, stream);
-        return launch_adapt_classes(a.src, adapt->bob_payload, (uint32_t)c->n, a.n_payload, a.n_frames, adapt->cls,
-                                    stream);
+// the class bytes are written by the launch, in the bit order of the kernel
+// that runs.
+struct DecodeIo {
+    uint32_t* corrected = nullptr;
+    const VerifyArgs* verify = nullptr;
+    const ClassArgs* adapt = nullptr;
+};
+
+// The launch path's debug options, read here and nowhere else on it.
+static LaunchOptions launch_options(const qkd_workspace* ws) {
+    const auto num = [ws](const char* name, bool wide = false) {
+        const DbgOpt e = debug_option(ws, name);
+        OptInt r;
+        r.set = (bool)e;
+        if (r.set) r.v = wide ? e.as_long() : (long)e.as_int();
+        return r;
     };
-    // QKD_MINSUM_STORE=global keeps the global-message-store min-sum (tests)
-    // (QKD_MINSUM_STORE=lds keeps the LDS-state kernel: tests)
+    LaunchOptions o;
+    if (debug_options_unset(ws)) return o;
     const DbgOpt ms_store = debug_option(ws, "QKD_MINSUM_STORE");
-    const bool ms_global = ms_store.is("global");
-    const bool ms_lds = ms_store.is("lds");
-    a.ms_sc = (flags & QKD_MINSUM_SELF_CORRECT) ? 1 : 0;
-    const bool classic = debug_option(ws, "QKD_DECODE_KERNEL").is("classic");
-    // min-sum: the split skeleton (every binary32 slot in LDS, the binary32
-    // rule's bit phase over DeviceCode::bit_code) when it applies, else the
-    // LDS-state kernel, else the global message store
-    if (rule == kRuleMinSum && !ms_global && !ms_lds && !classic && !a.trace && c->d_bit_code &&
-        c->n <= kMaxBitsSplit && c->m <= kMaxChecksSplit && c->max_dc <= 8) {
-        // (check degree <= 8: the additive mask table, seg_weight_entries)
-        const SplitLds Lm(c->n_pad, (c->n + 63) / 64, c->m, c->max_dv, c->max_dc <= 4 ? 4 : c->max_dc <= 6 ? 6 : 8,
-                          0, a.ms_sc ? 2 * c->n_tasks + (c->n + 63) / 64 : 0, 4, kLdsBytesMax);
-        if (Lm.S >= (uint32_t)((size_t)c->max_dv * c->n_pad) && Lm.bytes <= kLdsBytesMax)
-            rule = a.ms_sc ? kRuleMinSumSplitSc : kRuleMinSumSplit;
+    o.ms_global = ms_store.is("global");
+    o.ms_lds = ms_store.is("lds");
+    o.classic = debug_option(ws, "QKD_DECODE_KERNEL").is("classic");
+    if (const OptInt b = num("QKD_SPLIT_BUDGET", true); b.set) o.split_budget = std::min(kLdsBytesMax, (size_t)b.v);
+    o.fold_table = num("QKD_FOLD_TABLE");
+    o.spec_always = debug_option(ws, "QKD_SPEC_POLICY").is("always");
+    o.decode_grid = num("QKD_DECODE_GRID");
+    o.check_lanes = num("QKD_CHECK_LANES");
+    o.c2b_pad = num("QKD_C2B_PAD", true);
+    o.phase_timing = (bool)debug_option(ws, "QKD_PHASE_TIMING");
+    o.ilv = num("QKD_ILV");
+    o.ilv_grid = num("QKD_ILV_GRID");
+    o.syn_gather = debug_option(ws, "QKD_SYN_SLICED").is("0");
+    o.syn_pack_first = debug_option(ws, "QKD_SYN_BYTES").is("0");
+    return o;
+}
+
+// Stage 1, choose: the facts of the code and of the call, and the decision
+// (qkd_launch.h choose_decode). Touches neither the device nor the workspace.
+static DecodeChoice choose_launch(const qkd_code* c, const DecodeArgs& a, int mode, uint32_t flags, const DecodeIo& io,
+                                  const LaunchOptions& o, bool allow_ilv) {
+    const CodeFacts cf = code_facts(*c, c->d_bit_code ? true : false, c->d_ilv_slots ? true : false, c->cu_count);
+    LaunchFacts f;
+    f.mode = mode;
+    f.flags = flags;
+    f.n_frames = a.n_frames;
+    f.clamp_on = a.clamp_on != 0;
+    f.spec_cap = a.spec_cap;
+    f.ckpt_unsat = a.ckpt_unsat;
+    f.first_table = a.first_table;
+    f.tab2_entries = a.tab2_entries;
+    f.trace = a.trace != nullptr;
+    f.bits_out = a.bits_out != nullptr;
+    f.class_verify = a.vkey != nullptr;
+    f.adapt = io.adapt != nullptr;
+    return choose_decode(cf, f, o, allow_ilv);
+}
+
+// What stage 2 hands to stage 3: fn the kernel of kDecodeBlock threads (the
+// decoder; with the interleaved decoder ifn, the kernel of its hand-offs)
+struct LaunchPlan {
+    DecodeFn fn = nullptr, ifn = nullptr;
+    int grid = 0, igrid = 0;
+    const uint2* plan_enc = nullptr;
+};
+
+// Stage 2, prepare: everything of a launch that can fail -- the kernels of
+// the choice, their resident workgroups, the workspace's buffers, the encoded
+// plan. *no_ilv_memory (with a failure status and no error text): the
+// interleaved decoder's message lines could not be allocated (one region per
+// resident workgroup: ~6 GB at N = 60,000) and the choice was not forced: the
+// caller chooses again without it.
+static qkd_status prepare_launch(const qkd_code* c, qkd_workspace* ws, const DecodeChoice& ch, const LaunchOptions& o,
+                                 uint32_t n_frames, LaunchPlan& P, bool* no_ilv_memory) {
+    const bool split = ch.path != kPathClassic, ilv = ch.path == kPathSplitIlv;
+    DecodeFn exact = nullptr;
+    if (split) {
+        exact = split_kernel(ch.handoff);
+        P.fn = ch.decoder == ch.handoff ? exact : split_kernel(ch.decoder);
+        if (!exact || !P.fn)
+            return set_error(QKD_ERR_UNSUPPORTED, "no split kernel with the erasure rule for this launch");
+        if (ilv && !(P.ifn = ilv_kernel(ch.ilv)))
+            return set_error(QKD_ERR_UNSUPPORTED, "no interleaved kernel for this launch");
+    } else if (!(P.fn = classic_kernel(ch.decoder))) {
+        if (ch.decoder.era)
+            return set_error(QKD_ERR_UNSUPPORTED, "no classic kernel with the erasure rule for this launch");
+        // (a min-sum split rule whose layout a lowered QKD_SPLIT_BUDGET no longer fits)
+        return set_error(QKD_ERR_UNSUPPORTED, "no classic kernel for decode rule %d at check-degree bucket %d",
+                         ch.decoder.rule, ch.decoder.dc);
     }
-    if (rule == kRuleMinSum && !ms_global && decode_ms_fits(c, a.ms_sc != 0)) rule = kRuleMinSumLds;
-    if (a.ms_sc && rule != kRuleMinSumLds && rule != kRuleMinSumSplitSc)
-        return set_error(QKD_ERR_UNSUPPORTED, "self-corrected min-sum needs the split or the LDS-state min-sum "
-                                              "kernel (check degree <= 32, its state in LDS)");
-    if (a.ms_sc && rule == kRuleMinSumLds) rule = kRuleMinSumLdsSc;
+    // resident workgroups, at most one per frame
+    // (diagnostic: QKD_DECODE_GRID caps them, i.e. the frames in flight)
+    const size_t lds = split ? ch.split.bytes : ch.lds_bytes;
+    qkd_status s = decode_grid(c, split ? exact : P.fn, lds, &P.grid);
+    if (s != QKD_OK) return s;
+    P.grid = (int)std::min<size_t>((size_t)P.grid, n_frames);
+    if (o.decode_grid.set) P.grid = std::max(1, std::min(P.grid, (int)o.decode_grid.v));
+    if (P.fn != exact && split) {
+        // (the speculative kernel in the exact one's place: the fewer of the two)
+        int sgrid = 0;
+        s = decode_grid(c, P.fn, lds, &sgrid);
+        if (s != QKD_OK) return s;
+        P.grid = std::min(sgrid, P.grid);
+    }
+    if (ilv) {
+        P.fn = exact;
+        s = resident_grid(c, P.ifn, kIlvBlock, ch.ilv_lds.bytes, &P.igrid);
+        if (s != QKD_OK) return s;
+        if (P.igrid < 1) return set_error(QKD_ERR_UNSUPPORTED, "interleaved decoder cannot be resident");
+        P.igrid = (int)std::min<size_t>((size_t)P.igrid, ((size_t)n_frames + kIlvCols - 1) / kIlvCols);
+        // (QKD_ILV_GRID caps the workgroups: tests take columns through several frames)
+        if (o.ilv_grid.set) P.igrid = std::max(1, std::min(P.igrid, (int)o.ilv_grid.v));
+    }
+    s = ws_reserve_decode(ws, ch.need_c2b ? (size_t)P.grid : 0);
+    if (s != QKD_OK) return s;
+    if (ch.need_plan) {
+        s = plan_for_layout(c, ch.split, ch.bucket, &P.plan_enc, ch.esz, ch.cl_form);
+        if (s != QKD_OK) return s;
+    }
+    if (!ch.dead_ok)
+        return set_error(QKD_ERR_UNSUPPORTED, "code too large for the split decoder's slot words "
+                                              "(%zu global slots per frame)", ch.c2b_stride);
+    const size_t slots = (size_t)c->max_dv * c->n_pad;
+    if (ch.need_ckpt && ws->ckpt.reserve((size_t)P.grid * slots) != hipSuccess)
+        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of checkpoints",
+                         (size_t)P.grid * slots * sizeof(double));
+    if (ch.win_count && ws->win.reserve(2 * (size_t)ch.win_count) != hipSuccess)
+        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the policy windows");
+    if (ilv) {
+        const size_t need = (size_t)P.igrid * ch.istride;
+        if (ws->ilv.reserve(need) != hipSuccess) {
+            (void)hipGetLastError();
+            if (ch.ilv_forced)
+                return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of "
+                                                        "interleaved message lines", need * sizeof(double));
+            *no_ilv_memory = true;
+            return QKD_ERR_OUT_OF_MEMORY;
+        }
+        if (ws->fb_list.reserve(n_frames) != hipSuccess)
+            return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the hand-off list");
+    }
+    return ch.need_plan ? check_no_static_lds(P.fn) : QKD_OK;
+}
+
+// kModeClass: the class bytes of a launch, in the bit order of the view its
+// choice decodes in
+static hipError_t launch_classes(DecodeArgs& a, const DecodeChoice& ch, const ClassArgs* adapt, hipStream_t stream) {
+    if (ch.decoder.mode != kModeClass) return hipSuccess;
+    const bool internal = ch.path != kPathClassic;
+    a.src = internal ? adapt->src_int : adapt->src_orig;
+    a.cls = adapt->cls;
+    // (a round of qkd_reconcile_blind_batch: the frames of its list only)
+    if (adapt->blind)
+        return launch_blind_classes(a.src, internal ? adapt->blind->rank_int : adapt->blind->rank_orig,
+                                    adapt->bob_payload, *adapt->blind, (uint32_t)a.code.n, a.n_payload, a.n_frames,
+                                    adapt->cls, stream);
+    return launch_adapt_classes(a.src, adapt->bob_payload, (uint32_t)a.code.n, a.n_payload, a.n_frames, adapt->cls,
+                                stream);
+}
+
+// Stage 3, launch: the arguments' scratch fields from the choice and the
+// workspace, then the kernels. Nothing here can fail but a launch itself,
+// which matters on the keys path of the split decoders: frame_syn rewrites
+// ws->alice_w / bob_w in place in the internal bit order, and after it only
+// the decoder (which reads them in that order) may follow.
+static qkd_status launch_prepared(const qkd_code* c, qkd_workspace* ws, DecodeArgs& a, uint32_t flags,
+                                  const DecodeChoice& ch, const LaunchPlan& P, const LaunchOptions& o,
+                                  const DecodeIo& io, hipStream_t stream) {
+    const int mode = ch.decoder.mode;
+    const bool split = ch.path != kPathClassic;
+    a.ms_sc = (flags & QKD_MINSUM_SELF_CORRECT) ? 1 : 0;
     a.ms_scale = minsum_scale_of(flags);
     a.ms_offset = (float)((flags >> QKD_MINSUM_OFFSET_SHIFT) & 0xffu) / 64.0f;
-    // The split-store kernel (decode_split.hip) for the sum-product rules
-    // whenever its LDS layout fits; QKD_DECODE_KERNEL=classic keeps
-    // decode_kernel (A/B measurements, tests). Trace mode records the classic
-    // kernel's store.
-    const bool msr = rule == kRuleMinSumSplit || rule == kRuleMinSumSplitSc;
-    // codes past kMaxBitsSplit (up to kMaxBitsSplitLong): only the
-    // frame-interleaved decoder and its exact hand-off kernel (LONG) take
-    // them, on the keys path with the split view's arrays; otherwise the
-    // classic kernel below
-    const bool long_code = c->n > kMaxBitsSplit;
-    const bool long_ok = rule == kRuleSp64 && mode == kModeKeys && c->n <= kMaxBitsSplitLong && c->d_ilv_slots &&
-                         c->max_dc <= 16;
-    if ((rule == kRuleSp64 || rule == kRuleSp32 || msr) && !classic && !a.trace && (!long_code || long_ok) &&
-        c->m <= kMaxChecksSplit) {
-        // (a long code falls back to the classic kernel with the arguments as given)
-        const DecodeArgs a_in = a;
-        int sdc = 0;
-        DecodeFn sfn = long_code ? pick_split_long(a.clamp_on != 0, c->max_dc, &sdc)
-                                 : pick_split_decode(mode, rule, a.clamp_on != 0, c->max_dc, &sdc, era,
-                                                     mode == kModeClass && a.vkey != nullptr);
-        if (!sfn) return set_error(QKD_ERR_UNSUPPORTED, "no split kernel with the erasure rule for this launch");
-        const int esz = rule == kRuleSp64 ? 8 : 4;
-        // diagnostic: QKD_SPLIT_BUDGET lowers the LDS budget (fewer LDS slots)
-        size_t budget = kLdsBytesMax;
-        if (const DbgOpt b = debug_option(ws, "QKD_SPLIT_BUDGET")) budget = std::min(budget, (size_t)b.as_long());
-        // the speculative kernel (interval iterations, qkd_spec.h, exact
-        // replays in place) when it applies: QKD path with the folded first
-        // iteration, binary64 rule, clamped messages, bit degree <= kDvUnroll
-        // (the QKD path needs its folded first iteration; the LLR path starts from the LLRs)
-        const bool spec = rule == kRuleSp64 && a.spec_cap > 0 && a.clamp_on &&
-                          (mode == kModeLlr || a.first_table) && c->max_dv <= kDvUnroll && c->d_bit_code;
-        const bool ckpt = spec && mode == kModeKeys && a.ckpt_unsat > 0;
-        // its folded first iteration from a table (decode_split.hip fold_table_fill)
-        // (at most kFoldTabMaxEntries: the table's LDS comes off the message slots)
-        a.ftab_entries = (spec && !ckpt && mode == kModeKeys && a.tab2_entries &&
-                          c->n_pat * kFoldTabPat <= kFoldTabMaxEntries)
-                             ? c->n_pat * kFoldTabPat : 0;
-        // (QKD_FOLD_TABLE=0: the per-bit form; tests compare the two)
-        if (const DbgOpt e = debug_option(ws, "QKD_FOLD_TABLE")) if (e.as_int() == 0) a.ftab_entries = 0;
-        if (debug_option(ws, "QKD_SPEC_POLICY").is("always")) a.spec_always = 1u;
-        // (self-corrected min-sum: its previous-b2c ballot words and the
-        // frame's Bob words in the ftab region)
-        if (rule == kRuleMinSumSplitSc) a.ftab_entries = 2 * c->n_tasks + (c->n + 63) / 64;
-        // (the long-code hand-off kernel: the frame's Bob words there)
-        if (long_code) a.ftab_entries = std::max(a.ftab_entries, (c->n + 63) / 64);
-        const SplitLds L(c->n_pad, (c->n + 63) / 64, c->m, c->max_dv, sdc, a.tab2_entries, a.ftab_entries, esz,
-                         budget);
-        // (the binary32 rule's kernel keeps every slot in LDS: SplitStore<float, true>)
-        // (binary64: any share of the slots in LDS, the rest in the
-        // workgroup's global region; long codes keep most of them there)
-        const bool fits = rule != kRuleSp64 ? L.S >= (uint32_t)((size_t)c->max_dv * c->n_pad) : L.S >= 64;
-        if (L.bytes <= kLdsBytesMax && fits) {
-            int grid = 0;
-            qkd_status s = decode_grid(c, sfn, L.bytes, &grid);
-            if (s != QKD_OK) return s;
-            grid = (int)std::min<size_t>((size_t)grid, a.n_frames);
-            if (const DbgOpt g = debug_option(ws, "QKD_DECODE_GRID")) grid = std::max(1, std::min(grid, g.as_int()));
-            s = ws_reserve_decode(ws, (size_t)grid);
-            if (s != QKD_OK) return s;
-            a.code = c->view_split();     // the internal bit order (qkd_layout.h)
-            a.c2b = ws->c2b;
-            a.plan_enc = nullptr;
-            a.cl_split = 0;
-            ws->last_cl_form = 0;
-            ws->last_cl_tasks = 0;
-            ws->last_cl_rem_tasks = c->n_tasks;
-            if (rule == kRuleSp64 || msr) {
-                // the speculative check phases one check per lane (the default
-                // where the kernel has them: buckets 4 and 6, not the checkpointed
-                // form). QKD_CHECK_LANES: 0 edge-lane, 1 check-lane with the
-                // edge-lane remainder, 2 every check on a lane
-                int cl_form = 0;
-                if (spec && !ckpt && !long_code && rule == kRuleSp64 && c->cl_dc == sdc) {
-                    cl_form = kCheckLanesDefault;
-                    if (const DbgOpt e = debug_option(ws, "QKD_CHECK_LANES")) cl_form = std::max(0, std::min(2, e.as_int()));
-                }
-                s = plan_for_layout(c, L, sdc, &a.plan_enc, esz, cl_form);
-                if (s != QKD_OK) return s;
-                a.cl_split = 0;
-                if (cl_form != 0) {
-                    const ClHost& h = c->cl_host[cl_form - 1];
-                    a.cl_split = 0x80000000u | (uint32_t)h.cl_tasks | ((uint32_t)h.rem_tasks << 16);
-                    ws->last_cl_form = cl_form;
-                    ws->last_cl_tasks = h.cl_tasks;
-                    ws->last_cl_rem_tasks = h.rem_tasks;
-                }
-            }
-            const size_t slots = (size_t)c->max_dv * c->n_pad;
-            // elements of the message type, plus kC2bPad: the workgroups' regions
-            // start off a common alignment (measured: config 2 with the fold table
-            // has a region of 13184 slots, 4 % slower than 13248;
-            // QKD_C2B_PAD overrides the pad)
-            // Default: the region rounded up to an ODD multiple of kC2bPad
-            // slots (512 bytes), so consecutive regions never share an
-            // alignment above 512 bytes (13248 = 207 x 64 is the measured
-            // good case above); QKD_C2B_PAD adds a fixed pad instead.
-            if (const DbgOpt e = debug_option(ws, "QKD_C2B_PAD")) {
-                const size_t pad = std::min((size_t)e.as_long(), (size_t)c->n_pad);
-                a.c2b_stride = ((slots - L.S + 31) & ~(size_t)31) + pad;
-            } else {
-                size_t st = (slots - L.S + kC2bPad - 1) / kC2bPad;
-                if ((st & 1u) == 0) st++;
-                a.c2b_stride = st * kC2bPad;
-            }
-            // an encoded global slot word (kSlotGlobalBase + byte offset) must
-            // stay below kSlotLds, the LDS words' tag bit, and the region's
-            // buffer range below the dead slot word (qkd_decode.h kSlotDead)
-            static_assert(kSlotDead < kSlotLds, "the dead word bounds the global words");
-            if (rule == kRuleSp64 && !slot_dead_ok(L.bytes, a.c2b_stride))
-                return set_error(QKD_ERR_UNSUPPORTED, "code too large for the split decoder's slot words "
-                                                      "(%zu global slots per frame)", a.c2b_stride);
-            a.lds_budget = (uint32_t)budget;
-            a.counter = ws->counter;
-            const bool timing = (bool)debug_option(ws, "QKD_PHASE_TIMING");
-            a.phase = nullptr;
-            if (timing) {
-                a.phase = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws->counter.get()) + 64);
-                QKD_HIP(hipMemsetAsync(a.phase, 0, 64, stream));
-            }
-            a.replay_count = ws->counter + 1;
-            a.spec_replays = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws->counter.get()) + 120);
-            if (spec) {
-                // (a long code: the interleaved decoder speculates; no split speculation)
-                if (!long_code) {
-                    int xdc = 0, sgrid = 0;
-                    DecodeFn xfn = pick_split_spec(mode, c->max_dc, ckpt, &xdc);
-                    if (xdc != sdc)      // (the layout and the encoded plan are the bucket's)
-                        return set_error(QKD_ERR_UNSUPPORTED, "speculative kernel bucket %d != %d", xdc, sdc);
-                    s = decode_grid(c, xfn, L.bytes, &sgrid);
-                    if (s != QKD_OK) return s;
-                    sfn = xfn;
-                    grid = std::min(sgrid, grid);
-                }
-                if (ckpt && !long_code) {
-                    // one saved message store per resident workgroup
-                    const size_t need = (size_t)grid * slots;
-                    if (ws->ckpt.reserve(need) != hipSuccess)
-                        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of checkpoints",
-                                         need * sizeof(double));
-                    a.ckpt = ws->ckpt;
-                    a.ckpt_stride = (uint32_t)slots;
-                }
-            }
-            a.win = nullptr;
-            a.win_count = 0;
-            if (spec) {
-                // the in-launch policy's windows (zeroed below with the queue)
-                a.win_shift = kSpecWinShift;
-                a.win_lag = kSpecWinLag;
-                a.win_count = (uint32_t)((a.n_frames + (1u << kSpecWinShift) - 1) >> kSpecWinShift);
-                const size_t need = 2 * (size_t)a.win_count;
-                if (ws->win.reserve(need) != hipSuccess)
-                    return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the policy windows");
-                a.win = ws->win;
-            }
-            if (rule == kRuleSp64 || msr) {
-                s = check_no_static_lds(sfn);
-                if (s != QKD_OK) return s;
-            }
-            // Long codes (the split store keeps under a quarter of the slots
-            // in LDS): the frame-interleaved decoder (decode_ilv.hip), its
-            // hand-offs decoded by this split kernel from a frame list.
-            // QKD_ILV=1 / 0 forces it on / off (tests, A/B).
-            // (the target syndrome words in LDS when the three arrays fit, else
-            // in global memory: measured 30 % slower at N = 40,000, where
-            // they fit, and twice as fast as the split kernel at 60,000)
-            // (then also the uncertainty words, for M past ~37,000)
-            const bool tsg = IlvLds(c->m, false).bytes > kLdsBytesMax;
-            const bool ug = tsg && IlvLds(c->m, true).bytes > kLdsBytesMax;
-            const IlvLds IL(c->m, tsg, ug);
-            bool ilv = mode == kModeKeys && spec && !ckpt && !a.bits_out && a.first_table && c->d_ilv_slots &&
-                       IL.bytes <= kLdsBytesMax;
-            bool ilv_forced = false;
-            if (ilv) {
-                const DbgOpt ie = debug_option(ws, "QKD_ILV");
-                ilv_forced = (bool)ie;
-                ilv = ie ? ie.as_int() != 0
-                         : (size_t)L.S * 4 < slots && (size_t)a.n_frames * 2 >= (size_t)kIlvCols * c->cu_count;
-            }
-            DecodeFn ifn = nullptr;
-            int igrid = 0;
-            // (per workgroup: the message lines, the columns' key words, their
-            // target syndrome words: (M + 1) / 2 words, in doubles)
-            // rounded to 512 bytes: every workgroup's lines start on a cache
-            // line (an unaligned stride splits each line access in two)
-            // (and, ug, their uncertainty words as many again)
-            const size_t istride = (slots * kIlvCols + (size_t)((c->n + 63) / 64) * kIlvCols * 2 +
-                                    (ug ? 2 : 1) * (((size_t)(c->m + 1) / 2 + 1) / 2) + 63) & ~(size_t)63;
-            if (ilv) {
-                ifn = pick_ilv(c->ilv_rs, c->max_dc, tsg, ug);
-                QKD_HIP(hipFuncSetAttribute((const void*)ifn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)IL.bytes));
-                int per_cu = 0;
-                QKD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)ifn, kIlvBlock, IL.bytes));
-                if (per_cu < 1) return set_error(QKD_ERR_UNSUPPORTED, "interleaved decoder cannot be resident");
-                igrid = per_cu * c->cu_count;
-                igrid = (int)std::min<size_t>((size_t)igrid, ((size_t)a.n_frames + kIlvCols - 1) / kIlvCols);
-                // (QKD_ILV_GRID caps the workgroups: tests take columns through several frames)
-                if (const DbgOpt g = debug_option(ws, "QKD_ILV_GRID")) igrid = std::max(1, std::min(igrid, g.as_int()));
-                const size_t need = (size_t)igrid * istride;
-                if (ws->ilv.reserve(need) != hipSuccess) {
-                    // (one message region per resident workgroup: ~6 GB at N
-                    // = 60,000. Unless forced, the split kernel, which needs
-                    // far less, decodes the batch instead)
-                    (void)hipGetLastError();
-                    if (ilv_forced)
-                        return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate %zu B of "
-                                                                "interleaved message lines", need * sizeof(double));
-                    ilv = false;
-                }
-            }
-            // (a long code the interleaved decoder does not take: the classic kernel)
-            if (long_code && !ilv) {
-                a = a_in;
-                goto classic_path;
-            }
-            if (ilv && ws->fb_list.reserve(a.n_frames) != hipSuccess)
-                return set_error(QKD_ERR_OUT_OF_MEMORY, "workspace: cannot allocate the hand-off list");
-            // [0] frame queue, [1] replays: zeroed by frame_syn_kernel on the
-            // keys path (it runs first on this stream: block 0 writes both
-            // words), by a memset otherwise -- one branch, so a keys-mode
-            // launch without frame_syn cannot exist. Every check that can fail
-            // comes before it: frame_syn rewrites ws->alice_w / bob_w in place
-            // in the internal bit order, and after it only the decoder (which
-            // reads them in that order) may follow.
-            if (mode == kModeKeys) {
-                a.synw = ws->synw;
-                a.zout = ws->zout;
-                QKD_HIP(launch_frame_syn(a, stream, debug_option(ws, "QKD_SYN_SLICED").is("0"),
-                                         debug_option(ws, "QKD_SYN_BYTES").is("0")));
-            } else {
-                QKD_HIP(classes(true));
-                QKD_HIP(hipMemsetAsync(ws->counter, 0, 8, stream));
-                if (a.win) QKD_HIP(hipMemsetAsync(a.win, 0, 2 * (size_t)a.win_count * sizeof(uint32_t), stream));
-            }
-            QKD_HIP(decoder_event(ws, stream));
-            if (ilv) {
-                // [2] the hand-off queue, [3] the hand-off count
-                QKD_HIP(hipMemsetAsync(ws->counter + 2, 0, 8, stream));
-                DecodeArgs ai = a;
-                ai.ilv_store = ws->ilv;
-                ai.ilv_stride = istride;
-                ai.fb_list = ws->fb_list;
-                ai.fb_count = ws->counter + 3;
-                hipLaunchKernelGGL(ifn, dim3(igrid), dim3(kIlvBlock), IL.bytes, stream, ai);
-                // the hand-offs: the split kernel's exact iterations (their
-                // intervals could not certify; speculating again measured 1.7x
-                // slower), through the frame list
-                DecodeArgs af = a;
-                af.counter = ws->counter + 2;
-                af.frame_list = ws->fb_list;
-                af.frame_count = ws->counter + 3;
-                af.spec_cap = 0;
-                af.spec_always = 1;
-                af.phase = nullptr;       // (QKD_PHASE_TIMING: the interleaved kernel's phases)
-                int xdc = 0;
-                DecodeFn ffn = long_code ? pick_split_long(a.clamp_on != 0, c->max_dc, &xdc)
-                                         : pick_split_decode(mode, rule, a.clamp_on != 0, c->max_dc, &xdc);
-                if (xdc != sdc)
-                    return set_error(QKD_ERR_UNSUPPORTED, "exact split kernel bucket %d != %d", xdc, sdc);
-                // (the interleaved launch's error is read once and carried to
-                // decoder_event_close: a failed launch skips the hand-offs and
-                // fails the call instead of leaving stale outputs)
-                hipError_t le = hipGetLastError();
-                if (le == hipSuccess) {
-                    hipLaunchKernelGGL(ffn, dim3(grid), dim3(kDecodeBlock), L.bytes, stream, af);
-                    le = hipGetLastError();
-                }
-                QKD_HIP(decoder_event_close(ws, stream, le));
-            } else {
-                hipLaunchKernelGGL(sfn, dim3(grid), dim3(kDecodeBlock), L.bytes, stream, a);
-                QKD_HIP(decoder_event_close(ws, stream, hipGetLastError()));
-            }
-            if (mode == kModeKeys) QKD_HIP(launch_key_match(a, stream, corrected, verify));
-            return QKD_OK;
-        }
-    }
-classic_path:
-    const bool gt = decode_needs_gt(c, rule, a.tab2_entries);
-    if (gt) {                                     // large code: no per-bit LDS tables
-        a.first_table = 0;
-        a.tab2_entries = 0;
-    }
-    DecodeFn fn = pick_decode(mode, rule, a.clamp_on != 0, c->max_dc, gt, &dc, era,
-                              mode == kModeClass && a.vkey != nullptr);
-    if (!fn) return set_error(QKD_ERR_UNSUPPORTED, "no classic kernel with the erasure rule for this launch");
-    const size_t lds = decode_lds_bytes(c, dc, a.tab2_entries, rule, gt, a.ms_sc != 0);
-    int grid = 0;
-    qkd_status s = decode_grid(c, fn, lds, &grid);
-    if (s != QKD_OK) return s;
-    grid = (int)std::min<size_t>((size_t)grid, a.n_frames);
-    // diagnostic: QKD_DECODE_GRID caps the resident workgroups (frames in flight)
-    if (const DbgOpt g = debug_option(ws, "QKD_DECODE_GRID")) grid = std::max(1, std::min(grid, g.as_int()));
-    s = ws_reserve_decode(ws, (rule == kRuleMinSumLds || rule == kRuleMinSumLdsSc) ? 0 : (size_t)grid);   // no global messages
-    if (s != QKD_OK) return s;
-    a.code = c->view();
-    QKD_HIP(classes(false));
-    // (byte keys: the classic kernel reads them packed, in the original order)
-    if (mode == kModeKeys && a.bob_b) QKD_HIP(launch_pack_keys(a, stream));
+    a.spec_cap = ch.spec_cap;
+    a.first_table = ch.first_table;
+    a.tab2_entries = ch.tab2_entries;
+    a.code = split ? c->view_split() : c->view();      // (split: the internal bit order, qkd_layout.h)
     a.c2b = ws->c2b;
-    a.c2b_stride = (size_t)c->max_dv * c->n_pad;
-    // the workspace holds one total row per slot after all the message stores
-    a.totals = gt ? ws->c2b + ws->c2b.size() / ((size_t)c->max_dv + 1) * (size_t)c->max_dv : nullptr;
-    a.totals_stride = c->n_pad;
+    a.c2b_stride = ch.c2b_stride;
+    // the counter words: [0] frame queue, [1] replays, [2] the hand-off queue,
+    // [3] the hand-off count; + 64 B the phase clocks, + 120 B spec_replays
     a.counter = ws->counter;
-    QKD_HIP(hipMemsetAsync(ws->counter, 0, 4, stream));
-    const bool timing = (bool)debug_option(ws, "QKD_PHASE_TIMING");
-    a.phase = nullptr;
-    if (timing) {
-        a.phase = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws->counter.get()) + 64);
-        QKD_HIP(hipMemsetAsync(a.phase, 0, 64, stream));
+    char* const counter_bytes = reinterpret_cast<char*>(ws->counter.get());
+    a.phase = o.phase_timing ? reinterpret_cast<unsigned long long*>(counter_bytes + 64) : nullptr;
+    if (ch.cl_report) {
+        ws->last_cl_form = ch.cl_form;
+        ws->last_cl_tasks = ch.cl_tasks;
+        ws->last_cl_rem_tasks = ch.cl_rem_tasks;
+    }
+    if (!split) {
+        QKD_HIP(launch_classes(a, ch, io.adapt, stream));
+        // (byte keys: the classic kernel reads them packed, in the original order)
+        if (mode == kModeKeys && a.bob_b) QKD_HIP(launch_pack_keys(a, stream));
+        // the workspace holds one total row per slot after all the message stores
+        a.totals = ch.gt ? ws->c2b + ws->c2b.size() / ((size_t)c->max_dv + 1) * (size_t)c->max_dv : nullptr;
+        a.totals_stride = c->n_pad;
+        QKD_HIP(hipMemsetAsync(ws->counter, 0, 4, stream));
+        if (a.phase) QKD_HIP(hipMemsetAsync(a.phase, 0, 64, stream));
+        QKD_HIP(decoder_event(ws, stream));
+        hipLaunchKernelGGL(P.fn, dim3(P.grid), dim3(kDecodeBlock), ch.lds_bytes, stream, a);
+        QKD_HIP(decoder_event_close(ws, stream, hipGetLastError()));
+        // (the classic kernel wrote bits_out itself)
+        if (io.corrected)
+            QKD_HIP(launch_count_flips(a.bits_out, a.bob_b, (uint32_t)c->n, a.n_frames, io.corrected, stream));
+        if (io.verify) QKD_HIP(launch_verify_tags(a.bits_out, (uint32_t)c->n, a.n_frames, *io.verify, stream));
+        return QKD_OK;
+    }
+    a.plan_enc = P.plan_enc;
+    a.cl_split = ch.cl_split;
+    a.ftab_entries = ch.ftab_entries;
+    if (ch.spec_always) a.spec_always = 1u;
+    a.lds_budget = ch.lds_budget;
+    a.replay_count = ws->counter + 1;
+    a.spec_replays = reinterpret_cast<unsigned long long*>(counter_bytes + 120);
+    if (ch.need_ckpt) {
+        a.ckpt = ws->ckpt;
+        a.ckpt_stride = (uint32_t)((size_t)c->max_dv * c->n_pad);
+    }
+    // the in-launch policy's windows (zeroed below with the queue)
+    a.win = ch.win_count ? ws->win.get() : nullptr;
+    a.win_count = ch.win_count;
+    if (ch.spec) {
+        a.win_shift = kSpecWinShift;
+        a.win_lag = kSpecWinLag;
+    }
+    if (a.phase) QKD_HIP(hipMemsetAsync(a.phase, 0, 64, stream));
+    // [0] frame queue, [1] replays: zeroed by frame_syn_kernel on the keys
+    // path (it runs first on this stream: block 0 writes both words), by a
+    // memset otherwise -- one branch, so a keys-mode launch without frame_syn
+    // cannot exist
+    if (mode == kModeKeys) {
+        a.synw = ws->synw;
+        a.zout = ws->zout;
+        QKD_HIP(launch_frame_syn(a, stream, o.syn_gather, o.syn_pack_first));
+    } else {
+        QKD_HIP(launch_classes(a, ch, io.adapt, stream));
+        QKD_HIP(hipMemsetAsync(ws->counter, 0, 8, stream));
+        if (a.win) QKD_HIP(hipMemsetAsync(a.win, 0, 2 * (size_t)a.win_count * sizeof(uint32_t), stream));
     }
     QKD_HIP(decoder_event(ws, stream));
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(kDecodeBlock), lds, stream, a);
-    QKD_HIP(decoder_event_close(ws, stream, hipGetLastError()));
-    // (the classic kernel wrote bits_out itself)
-    if (corrected) QKD_HIP(launch_count_flips(a.bits_out, a.bob_b, (uint32_t)c->n, a.n_frames, corrected, stream));
-    if (verify) QKD_HIP(launch_verify_tags(a.bits_out, (uint32_t)c->n, a.n_frames, *verify, stream));
+    if (ch.path == kPathSplitIlv) {
+        QKD_HIP(hipMemsetAsync(ws->counter + 2, 0, 8, stream));
+        DecodeArgs ai = a;
+        ai.ilv_store = ws->ilv;
+        ai.ilv_stride = ch.istride;
+        ai.fb_list = ws->fb_list;
+        ai.fb_count = ws->counter + 3;
+        hipLaunchKernelGGL(P.ifn, dim3(P.igrid), dim3(kIlvBlock), ch.ilv_lds.bytes, stream, ai);
+        // the hand-offs: the split kernel's exact iterations (their
+        // intervals could not certify; speculating again measured 1.7x
+        // slower), through the frame list
+        DecodeArgs af = a;
+        af.counter = ws->counter + 2;
+        af.frame_list = ws->fb_list;
+        af.frame_count = ws->counter + 3;
+        af.spec_cap = 0;
+        af.spec_always = 1;
+        af.phase = nullptr;       // (QKD_PHASE_TIMING: the interleaved kernel's phases)
+        // (the interleaved launch's error is read once and carried to
+        // decoder_event_close: a failed launch skips the hand-offs and
+        // fails the call instead of leaving stale outputs)
+        hipError_t le = hipGetLastError();
+        if (le == hipSuccess) {
+            hipLaunchKernelGGL(P.fn, dim3(P.grid), dim3(kDecodeBlock), ch.split.bytes, stream, af);
+            le = hipGetLastError();
+        }
+        QKD_HIP(decoder_event_close(ws, stream, le));
+    } else {
+        hipLaunchKernelGGL(P.fn, dim3(P.grid), dim3(kDecodeBlock), ch.split.bytes, stream, a);
+        QKD_HIP(decoder_event_close(ws, stream, hipGetLastError()));
+    }
+    if (mode == kModeKeys) QKD_HIP(launch_key_match(a, stream, io.corrected, io.verify));
     return QKD_OK;
+}
+
+// One decode launch: choose, prepare, launch. `a` comes back with the values
+// the launch applied (decode_keys reads spec_cap and ckpt_unsat).
+static qkd_status launch_decode(const qkd_code* c, qkd_workspace* ws, DecodeArgs& a, int mode, uint32_t flags,
+                                hipStream_t stream, const DecodeIo& io = DecodeIo()) {
+    const LaunchOptions o = launch_options(ws);
+    DecodeChoice ch = choose_launch(c, a, mode, flags, io, o, true);
+    if (ch.status != QKD_OK) return set_error(ch.status, "%s", ch.message);
+    LaunchPlan P;
+    bool no_ilv_memory = false;
+    qkd_status s = prepare_launch(c, ws, ch, o, a.n_frames, P, &no_ilv_memory);
+    if (no_ilv_memory) {
+        // (the split kernel, which needs far less, decodes the batch instead;
+        // a long code: the classic kernel)
+        ch = choose_launch(c, a, mode, flags, io, o, false);
+        if (ch.status != QKD_OK) return set_error(ch.status, "%s", ch.message);
+        P = LaunchPlan();
+        s = prepare_launch(c, ws, ch, o, a.n_frames, P, &no_ilv_memory);
+    }
+    if (s != QKD_OK) return s;
+    return launch_prepared(c, ws, a, flags, ch, P, o, io, stream);
 }
 
 static qkd_status check_frames(size_t n_frames) {
@@ -2304,7 +2175,7 @@ static qkd_status decode_keys(const qkd_code* c, qkd_workspace* ws, size_t n_fra
         a.ckpt_unsat = (uint32_t)cu;
         if (cu == 0) a.spec_cap = 0;
     }
-    qkd_status st = launch_decode(c, ws, a, kModeKeys, flags, stream, corrected, verify);
+    qkd_status st = launch_decode(c, ws, a, kModeKeys, flags, stream, DecodeIo{corrected, verify, nullptr});
     if (st != QKD_OK || a.spec_cap == 0 || a.ckpt_unsat || ws->spec_stat_pending) return st;
     // (a QBER whose last two samples stayed under the switch is sampled again
     // only every kSpecStatEvery calls: each sample is a device-to-host copy
@@ -2484,8 +2355,8 @@ static qkd_status adaptive_run(const char* entry, const qkd_code* c, qkd_workspa
         class_verify_into(a, *cv, key);
     }
     const ClassArgs ca{ad->d_src_orig, ad->d_src_int, bob_payload, ws->cls};
-    return launch_decode(c, ws, a, kModeClass, flags & ~QKD_FLAG_ERASURES, (hipStream_t)stream, nullptr, nullptr,
-                         &ca);
+    return launch_decode(c, ws, a, kModeClass, flags & ~QKD_FLAG_ERASURES, (hipStream_t)stream,
+                         DecodeIo{nullptr, nullptr, &ca});
 }
 
 qkd_status qkd_reconcile_adaptive_batch(const qkd_code* c, qkd_workspace* ws, const qkd_adapt* ad,
@@ -2581,8 +2452,8 @@ static qkd_status blind_run(const char* entry, const qkd_code* c, qkd_workspace*
         a.frame_list = ws->blind_list;
         a.frame_count = count;
         if (cv) class_verify_into(a, *cv, vkey);
-        s = launch_decode(c, ws, a, kModeClass, flags & ~QKD_FLAG_ERASURES, (hipStream_t)stream, nullptr, nullptr,
-                          &ca);
+        s = launch_decode(c, ws, a, kModeClass, flags & ~QKD_FLAG_ERASURES, (hipStream_t)stream,
+                          DecodeIo{nullptr, nullptr, &ca});
         if (s != QKD_OK) return s;
     }
     return QKD_OK;

@@ -603,17 +603,24 @@ __global__ __launch_bounds__(kIlvBlock) void decode_ilv_kernel(DecodeArgs a) {
     }
 }
 
+// the instantiations: check rows of stride 16 with bucket 16, or of stride 8
+// with buckets 4 / 6 / 8
 template <bool TG, bool UG>
-static DecodeFn pick_ilv_dc(int rs, int max_dc) {
-    if (rs > 8) return decode_ilv_kernel<16, 16, TG, UG>;
-    if (max_dc <= 4) return decode_ilv_kernel<8, 4, TG, UG>;
-    if (max_dc <= 6) return decode_ilv_kernel<8, 6, TG, UG>;
-    return decode_ilv_kernel<8, 8, TG, UG>;
+static DecodeFn ilv_rows(const KernelKey& k) {
+    if (k.rs == 16 && k.dc == 16) return decode_ilv_kernel<16, 16, TG, UG>;
+    if (k.rs != 8) return nullptr;
+    switch (k.dc) {
+        case 4: return decode_ilv_kernel<8, 4, TG, UG>;
+        case 6: return decode_ilv_kernel<8, 6, TG, UG>;
+        case 8: return decode_ilv_kernel<8, 8, TG, UG>;
+    }
+    return nullptr;
 }
 
-DecodeFn pick_ilv(int rs, int max_dc, bool tsyn_global, bool xunc_global) {
-    if (xunc_global) return pick_ilv_dc<true, true>(rs, max_dc);
-    return tsyn_global ? pick_ilv_dc<true, false>(rs, max_dc) : pick_ilv_dc<false, false>(rs, max_dc);
+DecodeFn ilv_kernel(const KernelKey& k) {
+    if (k.kind != kKernelIlv || (k.ug && !k.tg)) return nullptr;
+    if (k.ug) return ilv_rows<true, true>(k);
+    return k.tg ? ilv_rows<true, false>(k) : ilv_rows<false, false>(k);
 }
 
 }  // namespace qkd

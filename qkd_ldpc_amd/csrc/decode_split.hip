@@ -527,7 +527,7 @@ __device__ __forceinline__ void ms_split_check_phase(const uint2* __restrict__ p
 // clamp(total - c2b_k) (:303-316); FOLD: the first iteration's messages
 // +-C_d (fold_first_message). The operations of the generic bit phase.
 constexpr int kSp32Chunk = 3;     // bit-phase rounds per load batch
-static_assert(kSp32Chunk - 1 <= kBitPadRounds, "per-bit arrays padded past the last load batch (host.cpp)");
+static_assert(kSp32Chunk - 1 <= kBitPadRounds, "per-bit arrays padded past the last load batch (qkd_layout.h)");
 // DV3: every bit has exactly kDvUnroll (3) checks (the reference's N = 10240
 // code): no per-row degree guards, so a round's loads, sums and stores are
 // straight-line code (the guarded form compiled each row's store to an
@@ -553,7 +553,7 @@ __device__ __forceinline__ void sp32_bit_phase(const DeviceCode& c, const Decode
 #pragma unroll
         for (int u = 0; u < kSp32Chunk; ++u) {
             const int i = tid + (r0 + u) * kDecodeBlock;
-            // (bit_code is padded to whole rounds, host.cpp build_code; rows
+            // (bit_code is padded to whole rounds, qkd_layout.h derive_code_layout; rows
             // k < max_dv of any i < n_pad are store slots: unconditional loads)
             bc[u] = c.bit_code[i];
 #pragma unroll
@@ -1071,7 +1071,7 @@ __device__ void fold_table_fill(const DeviceCode& c, const double* ctab, double 
 // rounds per load batch (2: measured -1 % per config-2 batch against 3, the
 // registers go to the check phases)
 constexpr int kIvChunk = QKD_IV_CHUNK;
-static_assert(kIvChunk - 1 <= kBitPadRounds, "per-bit arrays padded past the last load batch (host.cpp)");
+static_assert(kIvChunk - 1 <= kBitPadRounds, "per-bit arrays padded past the last load batch (qkd_layout.h)");
 // DV3: every bit has exactly kDvUnroll (3) checks (a column-weight-3 code,
 // like the reference's N = 10240 one): no per-degree guards, so the round is
 // straight-line code except one branch around the hard decision's syndrome
@@ -1150,8 +1150,8 @@ __device__ __forceinline__ void spec_bit_phase(const DeviceCode& c, const Decode
         for (int u = 0; u < kIvChunk; ++u) {
             const int i = tid + (r0 + u) * kDecodeBlock;
             const bool ok = i < cn;
-            // (bit_code and bit_pat are padded to whole rounds, host.cpp
-            // build_code: an unconditional load, no exec-mask branch around it)
+            // (bit_code and bit_pat are padded to whole rounds, qkd_layout.h
+            // derive_code_layout: an unconditional load, no exec-mask branch around it)
             bc[u] = c.bit_code[i];
             pat[u] = (FOLD && ftab) ? (uint32_t)c.bit_pat[i] : 0u;
             // (wave-uniform, said so: left to itself loop strength reduction
@@ -2164,7 +2164,7 @@ __global__ __launch_bounds__(kSynBlock) void frame_syn_kernel(DeviceCode c, uint
     // [kSynFrames][2 * words] pairs (Alice's 32-bit word, Bob's 32-bit word):
     // one 8-byte LDS read gives both keys' bit
     extern __shared__ uint2 kw[];
-    // the decoder's frame queue and replay count (decode.hip launch_decode:
+    // the decoder's frame queue and replay count (decode.hip launch_prepared:
     // this kernel runs first on the stream, in place of a memset)
     if (blockIdx.x == 0 && threadIdx.x < 2) counter[threadIdx.x] = 0;
     for (uint32_t i = blockIdx.x * kSynBlock + threadIdx.x; i < win_words; i += gridDim.x * kSynBlock) win[i] = 0;
@@ -2717,7 +2717,7 @@ hipError_t launch_frame_syn(const DecodeArgs& a, hipStream_t stream, bool gather
     // the bit-sliced form when its slices fit LDS and the compact rows exist
     // (gather, the QKD_SYN_SLICED option 0: frame_syn_kernel; tests compare the two)
     const size_t slds = (size_t)a.words * 64 * sizeof(uint32_t);
-    const bool sliced = a.code.chk_rows16 && slds <= 160 * 1024 && !gather;
+    const bool sliced = a.code.chk_rows16 && slds <= kLdsBytesMax && !gather;
     // the target syndrome given by the caller (qkd_reconcile_batch: a.syn set,
     // no Alice key): the GIVEN kernels, Bob's key alone
     const bool given = a.syn != nullptr;
@@ -2740,7 +2740,7 @@ hipError_t launch_frame_syn(const DecodeArgs& a, hipStream_t stream, bool gather
         // (the attribute on every launch, for the current device, as decode_grid
         // does for the decoder: no process-wide flag to race on or to skip for
         // a second device)
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytesMax);
         if (e != hipSuccess) return e;
         const dim3 grid((a.n_frames + kSlicedFrames - 1) / kSlicedFrames);
         if (given && bytes)
@@ -2820,88 +2820,76 @@ hipError_t launch_verify_tags(const uint8_t* bits, uint32_t n, uint32_t n_frames
     return hipGetLastError();
 }
 
-template <int MODE, int RULE, bool CLAMP, int SPEC = 0>
-static DecodeFn pick_split_dc(int max_dc, int* dc) {
-    if (max_dc <= 4) { *dc = 4; return decode_split_kernel<MODE, RULE, 4, CLAMP, SPEC>; }
-    if (max_dc <= 6) { *dc = 6; return decode_split_kernel<MODE, RULE, 6, CLAMP, SPEC>; }
-    if (max_dc <= 8) { *dc = 8; return decode_split_kernel<MODE, RULE, 8, CLAMP, SPEC>; }
-    if (max_dc <= 16) { *dc = 16; return decode_split_kernel<MODE, RULE, 16, CLAMP, SPEC>; }
-    *dc = 64;
-    return decode_split_kernel<MODE, RULE, 64, CLAMP, SPEC>;
-}
-
-DecodeFn pick_split_spec(int mode, int max_dc, bool ckpt, int* dc) {
-    if (ckpt) return pick_split_dc<kModeKeys, kRuleSp64, true, 2>(max_dc, dc);
-    return mode == kModeLlr ? pick_split_dc<kModeLlr, kRuleSp64, true, 1>(max_dc, dc)
-                            : pick_split_dc<kModeKeys, kRuleSp64, true, 1>(max_dc, dc);
-}
-
-template <int MODE, int RULE>
-static DecodeFn pick_split_clamp(bool clamp, int max_dc, int* dc) {
-    return clamp ? pick_split_dc<MODE, RULE, true>(max_dc, dc) : pick_split_dc<MODE, RULE, false>(max_dc, dc);
-}
-
-// the min-sum rules' buckets (the host takes them for check degree <= 8
-// only: the additive mask table)
-template <int MODE, int RULE, bool CLAMP>
-static DecodeFn pick_split_ms_dc(int max_dc, int* dc) {
-    if (max_dc <= 4) { *dc = 4; return decode_split_kernel<MODE, RULE, 4, CLAMP, 0>; }
-    if (max_dc <= 6) { *dc = 6; return decode_split_kernel<MODE, RULE, 6, CLAMP, 0>; }
-    *dc = 8;
-    return decode_split_kernel<MODE, RULE, 8, CLAMP, 0>;
-}
-template <int MODE, int RULE>
-static DecodeFn pick_split_ms(bool clamp, int max_dc, int* dc) {
-    return clamp ? pick_split_ms_dc<MODE, RULE, true>(max_dc, dc) : pick_split_ms_dc<MODE, RULE, false>(max_dc, dc);
-}
-
-template <int MODE>
-static DecodeFn pick_split_rule(int rule, bool clamp, int max_dc, int* dc) {
-    if (rule == kRuleMinSumSplit) return pick_split_ms<MODE, kRuleMinSumSplit>(clamp, max_dc, dc);
-    if (rule == kRuleMinSumSplitSc) return pick_split_ms<MODE, kRuleMinSumSplitSc>(clamp, max_dc, dc);
-    if (rule == kRuleSp32) return pick_split_clamp<MODE, kRuleSp32>(clamp, max_dc, dc);
-    return pick_split_clamp<MODE, kRuleSp64>(clamp, max_dc, dc);
-}
-
-// the exact keys-path kernel for codes past kMaxBitsSplit (LONG)
-DecodeFn pick_split_long(bool clamp, int max_dc, int* dc) {
-    if (max_dc <= 4) { *dc = 4; return clamp ? decode_split_kernel<kModeKeys, kRuleSp64, 4, true, 0, true>
-                                             : decode_split_kernel<kModeKeys, kRuleSp64, 4, false, 0, true>; }
-    if (max_dc <= 6) { *dc = 6; return clamp ? decode_split_kernel<kModeKeys, kRuleSp64, 6, true, 0, true>
-                                             : decode_split_kernel<kModeKeys, kRuleSp64, 6, false, 0, true>; }
-    if (max_dc <= 8) { *dc = 8; return clamp ? decode_split_kernel<kModeKeys, kRuleSp64, 8, true, 0, true>
-                                             : decode_split_kernel<kModeKeys, kRuleSp64, 8, false, 0, true>; }
-    *dc = 16;
-    return clamp ? decode_split_kernel<kModeKeys, kRuleSp64, 16, true, 0, true>
-                 : decode_split_kernel<kModeKeys, kRuleSp64, 16, false, 0, true>;
-}
-
-// the erasure rule's kernels (binary64, exact iterations): the LLR path with
-// QKD_FLAG_ERASURES, and the class-byte path
-template <int MODE, bool CLAMP, bool VFY = false>
-static DecodeFn pick_split_era_dc(int max_dc, int* dc) {
-    if (max_dc <= 4) { *dc = 4; return decode_split_kernel<MODE, kRuleSp64, 4, CLAMP, 0, false, true, VFY>; }
-    if (max_dc <= 6) { *dc = 6; return decode_split_kernel<MODE, kRuleSp64, 6, CLAMP, 0, false, true, VFY>; }
-    if (max_dc <= 8) { *dc = 8; return decode_split_kernel<MODE, kRuleSp64, 8, CLAMP, 0, false, true, VFY>; }
-    if (max_dc <= 16) { *dc = 16; return decode_split_kernel<MODE, kRuleSp64, 16, CLAMP, 0, false, true, VFY>; }
-    *dc = 64;
-    return decode_split_kernel<MODE, kRuleSp64, 64, CLAMP, 0, false, true, VFY>;
-}
-
-DecodeFn pick_split_decode(int mode, int rule, bool clamp, int max_dc, int* dc, bool era, bool vfy) {
-    if (era || mode == kModeClass) {
-        if (rule != kRuleSp64) return nullptr;
-        if (mode == kModeClass && vfy)
-            return clamp ? pick_split_era_dc<kModeClass, true, true>(max_dc, dc)
-                         : pick_split_era_dc<kModeClass, false, true>(max_dc, dc);
-        if (mode == kModeClass)
-            return clamp ? pick_split_era_dc<kModeClass, true>(max_dc, dc)
-                         : pick_split_era_dc<kModeClass, false>(max_dc, dc);
-        if (mode != kModeLlr) return nullptr;
-        return clamp ? pick_split_era_dc<kModeLlr, true>(max_dc, dc) : pick_split_era_dc<kModeLlr, false>(max_dc, dc);
+// The instantiations of decode_split_kernel, by key (qkd_launch.h KernelKey).
+// Buckets: 4 / 6 / 8 / 16 / 64; the min-sum rules 4 / 6 / 8 (the additive mask
+// table); the long-code kernel (LONG) 4 / 6 / 8 / 16. (The compiler emits the
+// kernels in the order these functions name them.)
+template <int MODE, int RULE, bool CLAMP, int SPEC = 0, bool ERA = false, bool VFY = false>
+static DecodeFn split_bucket(int dc) {
+    if (dc == 4) return decode_split_kernel<MODE, RULE, 4, CLAMP, SPEC, false, ERA, VFY>;
+    if (dc == 6) return decode_split_kernel<MODE, RULE, 6, CLAMP, SPEC, false, ERA, VFY>;
+    if (dc == 8) return decode_split_kernel<MODE, RULE, 8, CLAMP, SPEC, false, ERA, VFY>;
+    if constexpr (RULE != kRuleMinSumSplit && RULE != kRuleMinSumSplitSc) {
+        if (dc == 16) return decode_split_kernel<MODE, RULE, 16, CLAMP, SPEC, false, ERA, VFY>;
+        if (dc == 64) return decode_split_kernel<MODE, RULE, 64, CLAMP, SPEC, false, ERA, VFY>;
     }
-    return mode == kModeLlr ? pick_split_rule<kModeLlr>(rule, clamp, max_dc, dc)
-                            : pick_split_rule<kModeKeys>(rule, clamp, max_dc, dc);
+    return nullptr;
+}
+template <int MODE, int RULE, bool ERA = false, bool VFY = false>
+static DecodeFn split_clamp(const KernelKey& k) {
+    return k.clamp ? split_bucket<MODE, RULE, true, 0, ERA, VFY>(k.dc) : split_bucket<MODE, RULE, false, 0, ERA, VFY>(k.dc);
+}
+template <int MODE>
+static DecodeFn split_rule(const KernelKey& k) {
+    switch (k.rule) {
+        case kRuleMinSumSplit: return split_clamp<MODE, kRuleMinSumSplit>(k);
+        case kRuleMinSumSplitSc: return split_clamp<MODE, kRuleMinSumSplitSc>(k);
+        case kRuleSp32: return split_clamp<MODE, kRuleSp32>(k);
+        case kRuleSp64: return split_clamp<MODE, kRuleSp64>(k);
+    }
+    return nullptr;
+}
+
+DecodeFn split_kernel(const KernelKey& k) {
+    if (k.kind != kKernelSplit || k.gt) return nullptr;
+    // the speculative kernels (binary64 rule, clamp on): SPEC 1 for a mode,
+    // SPEC 2 the checkpointed variant (keys path: exact iterations first,
+    // interval ones from a checkpoint once few checks are unsatisfied)
+    if (k.spec) {
+        if (k.rule != kRuleSp64 || !k.clamp || k.lng || k.era || k.vfy) return nullptr;
+        if (k.spec == 2) return k.mode == kModeKeys ? split_bucket<kModeKeys, kRuleSp64, true, 2>(k.dc) : nullptr;
+        if (k.spec != 1) return nullptr;
+        return k.mode == kModeLlr ? split_bucket<kModeLlr, kRuleSp64, true, 1>(k.dc)
+                                  : k.mode == kModeKeys ? split_bucket<kModeKeys, kRuleSp64, true, 1>(k.dc) : nullptr;
+    }
+    // the exact keys-path kernel for codes past kMaxBitsSplit (LONG): the
+    // interleaved decoder's hand-offs
+    if (k.lng) {
+        if (k.mode != kModeKeys || k.rule != kRuleSp64 || k.era || k.vfy) return nullptr;
+        switch (k.dc) {
+            case 4: return k.clamp ? decode_split_kernel<kModeKeys, kRuleSp64, 4, true, 0, true>
+                                   : decode_split_kernel<kModeKeys, kRuleSp64, 4, false, 0, true>;
+            case 6: return k.clamp ? decode_split_kernel<kModeKeys, kRuleSp64, 6, true, 0, true>
+                                   : decode_split_kernel<kModeKeys, kRuleSp64, 6, false, 0, true>;
+            case 8: return k.clamp ? decode_split_kernel<kModeKeys, kRuleSp64, 8, true, 0, true>
+                                   : decode_split_kernel<kModeKeys, kRuleSp64, 8, false, 0, true>;
+            case 16: return k.clamp ? decode_split_kernel<kModeKeys, kRuleSp64, 16, true, 0, true>
+                                    : decode_split_kernel<kModeKeys, kRuleSp64, 16, false, 0, true>;
+        }
+        return nullptr;
+    }
+    // the erasure rule's kernels (binary64, exact iterations): the LLR path
+    // with QKD_FLAG_ERASURES, and the class-byte path (always; vfy: the
+    // instantiations that take the payload's verification tag)
+    if (k.era || k.mode == kModeClass) {
+        if (!k.era || k.rule != kRuleSp64) return nullptr;
+        if (k.mode == kModeClass)
+            return k.vfy ? split_clamp<kModeClass, kRuleSp64, true, true>(k)
+                         : split_clamp<kModeClass, kRuleSp64, true, false>(k);
+        return k.mode == kModeLlr && !k.vfy ? split_clamp<kModeLlr, kRuleSp64, true, false>(k) : nullptr;
+    }
+    if (k.vfy) return nullptr;
+    return k.mode == kModeLlr ? split_rule<kModeLlr>(k) : k.mode == kModeKeys ? split_rule<kModeKeys>(k) : nullptr;
 }
 
 }  // namespace qkd

@@ -63,6 +63,11 @@ DbgOpt debug_option(const qkd_workspace* ws, const char* name) {
     return o;
 }
 
+bool debug_options_unset(const qkd_workspace* ws) {
+    std::lock_guard<std::mutex> lock(g_dbg_mu);
+    return g_dbg.empty() && (!ws || ws->dbg.empty());
+}
+
 // Derive the layout (qkd_layout.h), check the device, upload. An array the
 // layout leaves empty is not uploaded: its device pointer stays null.
 template <class T, class H>

@@ -24,54 +24,10 @@ constexpr double kSpecCkptSwitch = 1.0 / 16.0;
 // Replay fraction above which speculation stops: within a launch for the
 // frames still to start (decode_split.hip), across calls for that QBER and up.
 constexpr double kSpecReplayMax = 1.0 / 6.0;
-// the in-launch policy's frame windows (DecodeArgs::win): 256 frames, decided
-// from the window 8 back (2048 frames earlier, ~8 frame-times at 256 resident
-// workgroups: by then it has almost always completed; with the window 4 back
-// the waits for a window's last slow frames cost 3.5 % per config-2 batch)
-constexpr uint32_t kSpecWinShift = 8;
-constexpr uint32_t kSpecWinLag = 8;
 // decode_keys samples the replay count of a QBER that twice stayed under
 // kSpecCkptSwitch only once every this many calls
 constexpr uint64_t kSpecStatEvery = 64;
 
-// Largest check degree the first-iteration table covers.
-constexpr int kFirstTableDeg = 16;
-
-
-enum DecodeMode : int {
-    kModeLlr = 0,  // qkd_decode_batch: caller LLRs + syndrome bytes
-    kModeKeys = 1, // QKD_LDPC path: packed alice/bob keys, LLR = +-log_p
-    // qkd_reconcile_adaptive_batch: one class byte per bit (DecodeArgs::cls, in
-    // the launched kernel's bit order) and the caller's syndrome bytes; the LLR
-    // of a bit is the level of its class: 0 +log_p, 1 -log_p, 2 +0.0
-    // (punctured), 3 +known (shortened), 4 +known / 5 -known (a punctured bit
-    // whose value Alice revealed: qkd_reconcile_blind_batch). Always with the
-    // erasure rule.
-    kModeClass = 2
-};
-
-// Check-node rule and message width (QKD_VARIANT_* in qkd_ldpc.h).
-//   kRuleSp64   the reference's sum-product in binary64, bit-exact
-//   kRuleSp32   the same schedule with binary32 messages and totals, the
-//               check rule in Gallager's form with the hardware exp2 / log2
-//               (a variant: not bit-exact to anything)
-//   kRuleMinSum normalised min-sum in binary32: c2b = scale * sign * min|b2c|
-//               over the other edges of the check (a variant, no transcendental)
-//   kRuleMinSumLds  the same min-sum with the frame's whole message state in
-//               LDS (per check: min1, min2, argmin, sign bits), no global
-//               message store; used when the state fits (decode_ms_fits)
-//   kRuleMinSumLdsSc  kRuleMinSumLds with Savin's self-correction
-//               (QKD_MINSUM_SELF_CORRECT) compiled in: its own kernel
-//               instantiation, so profiles attribute its time to it
-//   kRuleMinSumSplit / kRuleMinSumSplitSc  the same min-sum rules (plain /
-//               self-corrected) on the split decoder's skeleton: one binary32
-//               slot per edge, all in LDS, edge-parallel check phase
-//               (decode_split.hip ms_split_check_phase); used whenever that
-//               store fits (the default for codes like the reference's)
-enum DecodeRule : int {
-    kRuleSp64 = 0, kRuleSp32 = 1, kRuleMinSum = 2, kRuleMinSumLds = 3, kRuleMinSumLdsSc = 4,
-    kRuleMinSumSplit = 5, kRuleMinSumSplitSc = 6
-};
 template <int RULE> struct RuleMsg { using T = float; };
 template <> struct RuleMsg<kRuleSp64> { using T = double; };
 
@@ -284,42 +240,6 @@ __device__ __forceinline__ double class_llr(uint32_t cl, double log_p, double kn
     return (cl & 4u) ? r : v;
 }
 
-// The frame-interleaved decoder (decode_ilv.hip): kIlvCols frames per
-// workgroup in lockstep, one per lane of each 16-lane group; one message
-// line = one slot of the kIlvCols frames (128 bytes).
-constexpr int kIlvCols = 16;
-constexpr int kIlvCtlWords = 64;
-// its workgroup size (QKD_ILV_BLOCK; one workgroup per CU either way: its LDS)
-#ifndef QKD_ILV_BLOCK
-#define QKD_ILV_BLOCK 1024
-#endif
-constexpr int kIlvBlock = QKD_ILV_BLOCK;
-// the check phase's index ring: per 16-lane group four stages of kRingStage
-// words (a check's line indices, ~0 past its degree)
-constexpr int kRingStage = 16;
-// LDS: tsyn / xsyn / xunc, one word per check pair (check 2w in bits 0-15,
-// 2w + 1 in bits 16-31, bit = column), the column control words, the
-// first-iteration magnitudes by check degree.
-struct IlvLds {
-    size_t tsyn, xsyn, xunc, ctl, ctab, ring, bytes;
-    // tsyn_global: the target syndrome words in the workgroup's global region
-    // instead (decode_ilv_kernel's TG), for codes whose three arrays do not
-    // fit; xunc_global (UG, with TG): the uncertainty words there too (M past
-    // ~37,000: only the XOR-built syndrome stays in LDS)
-    __host__ __device__ IlvLds(int m, bool tsyn_global, bool xunc_global = false) {
-        const size_t mw2 = (size_t)(m + 1) / 2;
-        const size_t k = tsyn_global ? 0 : 1;
-        const size_t u = xunc_global ? 0 : 1;
-        tsyn = 0;
-        xsyn = k * mw2 * 4;
-        xunc = (k + 1) * mw2 * 4;
-        ctl = ((k + 1 + u) * mw2 * 4 + 15) & ~(size_t)15;
-        ctab = ctl + (size_t)kIlvCtlWords * 4;
-        ring = ctab + (size_t)(kFirstTableDeg + 1) * 8;
-        bytes = ring + (size_t)(kIlvBlock / kIlvCols) * 4 * kRingStage * 4;
-    }
-};
-
 // Phase-clock accumulation (diagnostic; a wave-uniform test when off). Each
 // mark adds straight to the global slot, so nothing is indexed dynamically in
 // registers (an accumulator array would live in scratch).
@@ -360,62 +280,11 @@ __device__ __forceinline__ bool block_any(bool p, uint32_t* flags, uint32_t& k) 
 }
 
 
-// Syndrome bit arrays hold whole 64-check groups (written by one ballot each).
-__host__ __device__ inline int decode_m_words(int m) { return ((m + 63) / 64) * 2; }
-
-// LDS layout of decode_kernel (bytes):
-//   total  [n_pad]          bit totals (the reference's `total`, :256-267), message width
-//   tsyn   [m_words]        target syndrome, one bit per check
-//   xsyn   [m_words]        syndrome of the current hard decision (XOR-built)
-//   qsyn   [m_words]        QKD path: sign of each check's first-iteration product
-//   tval   [NW][64 + DC]    per-wave tanh values for the in-check products
-//                           (prologue: the frame's Alice + Bob words)
-//   ctab   [kFirstTableDeg+1] first-iteration message magnitudes by degree
-//   tab2   [tab2_entries]   second-iteration tanh table
-//   t2idx  [n_pad]          per-bit base index into tab2 (uint16)
-//   ctl    [4]              frame index, block_any flags
-//   cst    [m] (uint4)      kRuleMinSumLds: per-check min-sum state (ms_state)
-struct DecodeLds {
-    size_t tsyn, xsyn, qsyn, tval, ctab, tab2, t2idx, ctl, cst, czf, bytes;
-    // total_esz: bytes per bit total in LDS (0: the totals live in global
-    // memory, large codes); cst_checks: min-sum state of that many checks (16
-    // bytes each, and with zf a word of zero flags each, self-corrected min-sum)
-    __host__ __device__ DecodeLds(int n_pad, int n_words, int m, int dc, int tab2_entries, int total_esz,
-                                  int cst_checks = 0, int row_esz = 0, bool zf = false) {
-        const int m_words = decode_m_words(m);
-        const int esz = row_esz ? row_esz : total_esz;
-        tsyn = ((size_t)n_pad * total_esz + 15) & ~(size_t)15;
-        xsyn = tsyn + (size_t)m_words * 4;
-        qsyn = xsyn + (size_t)m_words * 4;
-        tval = (qsyn + (size_t)m_words * 4 + 15) & ~(size_t)15;
-        // the tanh rows double as the prologue's staging area for the frame's
-        // Alice and Bob words
-        const size_t rows = (size_t)(kDecodeBlock / 64) * (64 + dc) * esz;
-        const size_t stage = (size_t)n_words * 16;
-        ctab = (tval + (rows > stage ? rows : stage) + 15) & ~(size_t)15;
-        tab2 = ctab + (size_t)(kFirstTableDeg + 1) * 8;
-        t2idx = tab2 + (size_t)tab2_entries * 8;
-        ctl = (t2idx + (tab2_entries ? (size_t)n_pad * 2 : 0) + 15) & ~(size_t)15;
-        cst = ctl + 16;
-        czf = cst + (size_t)cst_checks * 16;
-        bytes = czf + (zf ? (size_t)cst_checks * 4 : 0);
-    }
-};
-
-// Bit phase: message rows per bit loaded ahead of the ordered sum, and rounds
-// (bits tid + r*kDecodeBlock) per load batch.
-constexpr int kDvUnroll = 3;
-// fold table entries per degree pattern: 2^(1 + kDvUnroll) sign codes x
-// (kDvUnroll psi bounds + the hard decision)
-constexpr int kFoldTabPat = (2 << kDvUnroll) * (kDvUnroll + 1);
 constexpr int kBitChunk = 5;
 #ifndef QKD_SPEC_EXACT_CHUNK
 #define QKD_SPEC_EXACT_CHUNK 2
 #endif
 constexpr int kBitChunkSpec = QKD_SPEC_EXACT_CHUNK;     // the exact iterations inside the speculative kernel
-// the second-iteration table index and the first-message fold read a bit's
-// messages from the unrolled rows only
-static_assert(kTab2MaxDv <= kDvUnroll, "tables need every row of their bits unrolled");
 // Plan-walking loops outside the check phase load this many tasks' plan words
 // per trip (the plan carries kPlanPadTasks >= kPlanGroup * NW idle tasks).
 constexpr int kPlanGroup = 4;
@@ -679,94 +548,9 @@ __device__ void second_table_fill(const DeviceCode& c, const double* ctab, doubl
 }
 
 // ---- split message store (decode_split.hip) ----------------------------------
-// LDS layout of decode_split_kernel (bytes):
-//   tsyn, xsyn, qsyn [m_words]   target syndrome / XOR-built syndrome / first-product signs
-//   xunc  [m_words]              speculative rounds: checks with an uncertain hard decision
-//   zw    [n_pad / 64] uint64    hard decision of the last bit phase, one bit per bit
-//   aw    [n_words] uint64       keys path: Alice's key words (the epilogue's compare)
-//   tval  [NW][64 + DC] T        per-wave rows for the in-check products
-//                                (prologue: the frame's Bob words)
-//   ctab  [kFirstTableDeg + 1]   first-iteration message magnitudes by degree
-//   tab2  [tab2_entries]         second-iteration tanh table
-//   ftab  [ftab_entries]         speculative kernel: the folded first
-//                                iteration's psi bounds and hard decisions
-//   ctl   [12]                   [1] next frame, [4..5] round flags, [7] key mismatch (decode_split.hip)
-//   wtab  [dc][dc][dc] float     extrinsic-sum weights by (degree, position, k) (dc <= 8)
-//   msg   [S + 64] T             message slots 0 .. S-1 (slots S .. max_dv*n_pad-1
-//                                live in the workgroup's global region), then
-//                                one trash slot per lane
-// S is as many slots as the budget leaves after the rest, in whole 64s.
-// Weights of a check phase's extrinsic sums: lane at position p of a
-// segment of degree deg sums row entry k with weight (k < deg && k != p).
-// Buckets up to 8 read them from an LDS table (wtab[deg - 1][p][k], two
-// per ds_read_b64) instead of extracting and converting mask bits per entry.
-// Buckets DC <= 8 index their segment-weight rows by deg * 8 + p (encode_seg),
-// so a lane's degree is one bit-field read of its plan word instead of a
-// division by DC (rows of degree 0 and p >= DC unused; -3 VALU per check-phase
-// task; with the check phases' select-free row entries -3.4 % per config-2
-// batch, profiles/r06_ab.txt)
-__host__ __device__ inline int seg_weight_entries(int dc) { return dc <= 8 ? 9 * 8 * dc : 0; }
-
-struct SplitLds {
-    size_t tsyn, xsyn, qsyn, xunc, zw, aw, tval, ctab, tab2, ftab, ctl, wtab, msg, bytes;
-    uint32_t S;
-    __host__ __device__ SplitLds(int n_pad, int n_words, int m, int max_dv, int dc, int tab2_entries,
-                                 int ftab_entries, int esz, size_t budget) {
-        const int m_words = decode_m_words(m);
-        tsyn = 0;
-        qsyn = tsyn + (size_t)m_words * 4;
-        xsyn = qsyn + (size_t)m_words * 4;
-        xunc = xsyn + (size_t)m_words * 4;
-        zw = (xunc + (size_t)m_words * 4 + 15) & ~(size_t)15;
-        // keys path: Alice's words of the frame, loaded with the prologue's
-        // batch for the epilogue's key compare
-        aw = (zw + (size_t)(n_pad / 64) * 8 + 15) & ~(size_t)15;
-        tval = (aw + (size_t)n_words * 8 + 15) & ~(size_t)15;
-        const size_t rows = (size_t)(kDecodeBlock / 64) * (64 + dc) * esz;
-        const size_t stage = (size_t)n_words * 8;     // (the prologue stages Bob's words there)
-        ctab = (tval + (rows > stage ? rows : stage) + 15) & ~(size_t)15;
-        tab2 = ctab + (size_t)(kFirstTableDeg + 1) * 8;
-        ftab = (tab2 + (size_t)tab2_entries * 8 + 15) & ~(size_t)15;
-        ctl = (ftab + (size_t)ftab_entries * 8 + 15) & ~(size_t)15;
-        wtab = ctl + 48;
-        msg = (wtab + (size_t)seg_weight_entries(dc) * 4 + 15) & ~(size_t)15;
-        const size_t slots = (size_t)max_dv * n_pad;
-        // 64 trash slots follow the S message slots (decode_split.hip SplitStore)
-        const size_t fit = budget > msg + 64 * (size_t)esz ? (budget - msg) / (size_t)esz - 64 : 0;
-        // (a multiple of 64: with n_pad one too, a wave's 64 consecutive bits
-        // of one row are all in LDS or all global, SplitStore::ld_row)
-        S = (uint32_t)(slots < fit ? slots : fit) & ~63u;
-        bytes = msg + ((size_t)S + 64) * esz;
-    }
-};
-
-// Encoded message-slot words of the split decoder's check phases (its plan,
-// DecodeArgs::plan_enc, one per LDS layout): slot x < S (in LDS) as
-// kSlotLds | its byte address from the dynamic LDS base; a global slot as
-// kSlotGlobalBase + its byte offset in the workgroup's region. The buffer
-// descriptor of the region starts kSlotGlobalBase bytes early and spans
-// kSlotGlobalBase + the region, so LDS words fail its range check (loads give
-// 0, stores are dropped), and global words are LDS addresses past any
-// allocation (the same there: tools/mb/lds_oob.hip measures it on gfx950).
-constexpr uint32_t kSlotLds = 0x80000000u;
-constexpr uint32_t kSlotGlobalBase = 0x40000u;
+// (its LDS layout SplitLds and the slot words' constants: qkd_launch.h)
 __host__ __device__ inline uint32_t encode_slot(uint32_t x, uint32_t S, uint32_t msg, uint32_t esz) {
     return x < S ? (kSlotLds | (msg + x * esz)) : (kSlotGlobalBase + (x - S) * esz);
-}
-// The reserved word of a slot that does not exist (the check-lane plan's
-// entries past a check's degree): out of range for BOTH halves of an access,
-// so it loads 0 and its store goes nowhere. As an LDS address it is past any
-// allocation in the way every global word is, whatever number of low address
-// bits the hardware compares (all of them are set); as a buffer offset it is
-// past the descriptor's range as long as the range ends at or below it.
-// slot_dead_ok says so for an LDS allocation and a region of global slots (8
-// bytes each): plan_for_layout checks every layout it encodes against the
-// largest region a launch can give it, launch_decode the region it gives.
-// 8-byte aligned, as every slot word.
-constexpr uint32_t kSlotDead = 0x7ffffff8u;
-static_assert((kSlotDead & (kSlotLds | 7u)) == 0, "a global-form word, aligned");
-__host__ __device__ inline bool slot_dead_ok(size_t lds_bytes, size_t global_slots) {
-    return lds_bytes <= kSlotGlobalBase && (size_t)kSlotGlobalBase + global_slots * 8 <= kSlotDead;
 }
 
 // The encoded plan's second word (check-degree bucket DC), the lane's
@@ -806,21 +590,11 @@ __host__ __device__ inline size_t cl_words_offset(int n_tasks, int rem_tasks) {
 }
 
 using DecodeFn = void (*)(DecodeArgs);
-// decode_split.hip: the split-store kernel for (mode, rule in {kRuleSp64,
-// kRuleSp32}, clamp, check-degree bucket); *dc receives the bucket.
-// era (binary64 rule, kModeLlr; kModeClass always): the erasure rule's kernels.
-// vfy (kModeClass): the instantiations that take the payload's verification
-// tag (DecodeArgs::vkey != nullptr).
-DecodeFn pick_split_decode(int mode, int rule, bool clamp, int max_dc, int* dc, bool era = false, bool vfy = false);
-// the exact keys-path split kernel for codes past kMaxBitsSplit bits (up to
-// kMaxBitsSplitLong; check degree <= 16): the interleaved decoder's hand-offs
-DecodeFn pick_split_long(bool clamp, int max_dc, int* dc);
-// The speculative kernel (binary64 rule, clamp on) for a mode; ckpt: the
-// checkpointed variant (keys path: exact iterations first, interval ones from
-// a checkpoint once few checks are unsatisfied).
-DecodeFn pick_split_spec(int mode, int max_dc, bool ckpt, int* dc);
-// the frame-interleaved decoder (decode_ilv.hip) for check-row stride rs (8 or 16)
-DecodeFn pick_ilv(int rs, int max_dc, bool tsyn_global, bool xunc_global = false);
+// The kernel of a key (qkd_launch.h KernelKey), one lookup per translation
+// unit: decode_split.hip (kKernelSplit), decode_ilv.hip (kKernelIlv); the
+// classic kernels' is decode.hip's own. nullptr: no such instantiation.
+DecodeFn split_kernel(const KernelKey& k);
+DecodeFn ilv_kernel(const KernelKey& k);
 // decode_split.hip, kModeKeys: the kernels around the split decoder.
 // Before: a.synw from the packed keys. After: key_ok / bits_out from a.zout.
 // gather: the gather kernel instead of the bit-sliced one; pack_first: byte
@@ -843,7 +617,7 @@ hipError_t launch_count_flips(const uint8_t* bits, const uint8_t* bob, uint32_t 
 // qkd_reconcile_verify_batch after the classic kernel): one launch, no workspace
 hipError_t launch_verify_tags(const uint8_t* bits, uint32_t n, uint32_t n_frames, const VerifyArgs& v,
                               hipStream_t stream);
-// adapt.hip, kModeClass: what launch_decode needs of a qkd_adapt and its call
+// adapt.hip, kModeClass: what the decode launch needs of a qkd_adapt and its call
 // (the plan's maps in both bit orders, Bob's payload, the workspace's class
 // bytes), and the kernel that writes the class bytes of F frames from a map:
 // cls[f * n + i] = src[i] >= 0 ? payload[f * n_payload + src[i]] & 1

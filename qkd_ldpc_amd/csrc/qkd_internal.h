@@ -12,15 +12,10 @@
 
 #include "../../include/qkd_ldpc.h"
 #include "qkd_device.h"
+#include "qkd_launch.h"
 #include "qkd_layout.h"
 
 namespace qkd {
-
-constexpr int kFoldTabMaxEntries = 1024;   // speculative fold table (decode_split.hip), 8 B each
-// speculative check phases (decode_split.hip), buckets 4 and 6: 1 one check per
-// lane with an edge-lane remainder, 0 one edge per lane (QKD_CHECK_LANES overrides)
-constexpr int kCheckLanesDefault = 1;
-constexpr size_t kC2bPad = 64;            // split kernels: slots added to each workgroup's global region
 
 static_assert(sizeof(U2) == sizeof(uint2) && alignof(U2) <= alignof(uint2), "U2 is uint2's layout");
 
@@ -264,6 +259,8 @@ struct DbgOpt {
     bool is(const char* s) const { return set && v == s; }
 };
 DbgOpt debug_option(const qkd_workspace* ws, const char* name);
+// no option is set, on the workspace or process-wide (the product path: one lock, no lookup)
+bool debug_options_unset(const qkd_workspace* ws);
 
 #define QKD_HIP(call)                                                                     \
     do {                                                                                  \
