@@ -592,16 +592,17 @@ __host__ __device__ inline size_t cl_words_offset(int n_tasks, int rem_tasks) {
 using DecodeFn = void (*)(DecodeArgs);
 // The kernel of a key (qkd_launch.h KernelKey), one lookup per translation
 // unit: decode_split.hip (kKernelSplit), decode_ilv.hip (kKernelIlv); the
-// classic kernels' is decode.hip's own. nullptr: no such instantiation.
+// classic kernels' (decode.hip classic_kernel) is declared in qkd_host.h.
+// nullptr: no such instantiation.
 DecodeFn split_kernel(const KernelKey& k);
 DecodeFn ilv_kernel(const KernelKey& k);
-// decode_split.hip, kModeKeys: the kernels around the split decoder.
-// Before: a.synw from the packed keys. After: key_ok / bits_out from a.zout.
+// kModeKeys: the kernels around the split decoder. Before (frame_syn.hip):
+// a.synw from the packed keys. After (frame_out.hip): key_ok / bits_out from a.zout.
 // gather: the gather kernel instead of the bit-sliced one; pack_first: byte
 // keys packed by pack_kernel first (the QKD_SYN_SLICED / QKD_SYN_BYTES options)
 // a.syn set (qkd_reconcile_batch): the given-target kernels, Bob's key alone.
 hipError_t launch_frame_syn(const DecodeArgs& a, hipStream_t stream, bool gather = false, bool pack_first = false);
-// decode.hip: a.alice_b / a.bob_b -> a.alice_w / a.bob_w (original bit order);
+// bits.hip: a.alice_b / a.bob_b -> a.alice_w / a.bob_w (original bit order);
 // a.alice_b == nullptr: Bob's key alone
 hipError_t launch_pack_keys(const DecodeArgs& a, hipStream_t stream);
 // corrected (qkd_reconcile_batch, with a.bits_out and a.bob_b): the unpack

@@ -82,7 +82,7 @@ struct DeviceCode {
 
 }  // namespace qkd
 
-// the speculation policy's record of one QBER (decode.hip decode_keys): clean =
+// the speculation policy's record of one QBER (api.hip decode_keys): clean =
 // consecutive replay samples under the switch; skip = calls since the last
 // sample once clean >= 2 (sampled every kSpecStatEvery calls)
 struct SpecClean {
@@ -101,22 +101,22 @@ struct qkd_workspace {
     qkd::DevBuf<double> c2b;
     // dynamic frame queue counter (zeroed per launch)
     qkd::DevBuf<uint32_t> counter;
-    // the check-phase form of the last split-decoder launch (decode.hip;
+    // the check-phase form of the last split-decoder launch (launch.hip;
     // qkd_debug_check_lanes): QKD_CHECK_LANES' value as applied, its check-lane
     // tasks and the edge-lane tasks of its remainder; -1 before any launch
     int last_cl_form = -1, last_cl_tasks = 0, last_cl_rem_tasks = 0;
     // packed alice / bob keys (uint64 words) for the fused paths
     qkd::DevBuf<uint64_t> alice_w, bob_w;
     size_t key_frames = 0;             // alice_w, bob_w, synw and zout hold this many frames
-    // split decoder, keys path (decode_split.hip): per frame the target and
-    // first-product syndrome words (frame_syn_kernel) and the hard decision
-    // words the decoder leaves for key_match_kernel; sized with the keys
+    // split decoder, keys path: per frame the target and first-product
+    // syndrome words (frame_syn.hip) and the hard decision words the decoder
+    // leaves for launch_key_match (frame_out.hip); sized with the keys
     qkd::DevBuf<uint32_t> synw;
     qkd::DevBuf<uint64_t> zout;
     // keygen shuffle scratch (ne words per frame)
     qkd::DevBuf<uint32_t> low;
     hipEvent_t done = nullptr;
-    // speculation policy across calls (decode.hip, decode_keys): the replay
+    // speculation policy across calls (api.hip, decode_keys): the replay
     // count of the last speculative call comes back asynchronously; a QBER
     // point whose frames were replayed too often (kSpecCkptSwitch) switches it
     // and every higher QBER on this workspace to the checkpointed speculation
@@ -157,7 +157,7 @@ struct qkd_workspace {
     uint64_t dec_pairs_folded = 0;
 
     // the events and the pinned word, with the workspace's device current
-    // (decode.hip); the buffers free themselves
+    // (launch.hip); the buffers free themselves
     ~qkd_workspace();
 };
 
@@ -269,10 +269,5 @@ bool debug_options_unset(const qkd_workspace* ws);
             return ::qkd::set_error(QKD_ERR_DEVICE, "%s failed: %s (%s:%d)", #call,       \
                                     hipGetErrorString(e_), __FILE__, __LINE__);           \
     } while (0)
-
-// Workspace helpers (decode.hip).
-qkd_status ws_reserve_decode(qkd_workspace* ws, size_t slots);
-qkd_status ws_reserve_keys(qkd_workspace* ws, size_t frames, size_t low_words);
-qkd_workspace* resolve_ws(const qkd_code* code, qkd_workspace* ws);
 
 }  // namespace qkd

@@ -1,4 +1,4 @@
-// qkd_launch.h — the decision of a decode launch (decode.hip launch_decode:
+// qkd_launch.h — the decision of a decode launch (launch.hip launch_decode:
 // choose, prepare, launch): which kernels decode a batch, with which LDS
 // layouts, buckets and strides, from the scalars of the code, of the call and
 // of the debug options. No HIP header and no device call: choose_decode is a
@@ -225,7 +225,7 @@ static_assert(kLdsBytesMax <= kSlotGlobalBase, "global slot words must lie past 
 // bits the hardware compares (all of them are set); as a buffer offset it is
 // past the descriptor's range as long as the range ends at or below it.
 // slot_dead_ok says so for an LDS allocation and a region of global slots (8
-// bytes each): plan_for_layout (decode.hip) checks every layout it encodes
+// bytes each): plan_for_layout (launch.hip) checks every layout it encodes
 // against the largest region a launch can give it, choose_decode the region
 // it gives. 8-byte aligned, as every slot word.
 constexpr uint32_t kSlotDead = 0x7ffffff8u;
@@ -283,7 +283,7 @@ struct OptInt {
     long v = 0;
 };
 // Every debug option of the launch path (qkd_debug_set_option), parsed once
-// per call (decode.hip launch_options): the workspace's value, else the
+// per call (launch.hip launch_options): the workspace's value, else the
 // process-wide one.
 struct LaunchOptions {
     bool ms_global = false, ms_lds = false;   // QKD_MINSUM_STORE=global / =lds

@@ -52,7 +52,7 @@ struct CodeHost {
     // the split kernels' internal bit order (empty without the split view)
     std::vector<int32_t> perm;
     int32_t chk_rs = 0, ilv_rs = 0;     // row strides of chk_rows16 / ilv_slots, 0: none
-    // the slot plan (its encoded forms by LDS layout: plan_for_layout, decode.hip)
+    // the slot plan (its encoded forms by LDS layout: plan_for_layout, launch.hip)
     std::vector<U2> plan_slot;
     // the check-lane plans (cl_dc = their bucket, 0: none -- check degree past
     // 6 or no bit_code): [0] the split form (whole rounds of check-lane tasks

@@ -160,7 +160,7 @@ QKD_RHD void shuffle_low_positions(Xoshiro256pp& g, uint32_t n, uint32_t ne, Low
 }
 
 // ---------------------------------------------------------------------------
-// Jump-ahead for the parallel key generator (decode.hip: keygen_fast_kernel).
+// Jump-ahead for the parallel key generator (keygen.hip: keygen_fast_kernel).
 //
 // xoshiro256's state transition (next() without its output scrambler) is
 // linear over GF(2)^256, so "advance by j draws" is a 256x256 bit matrix T^j.

@@ -7,7 +7,7 @@
 //   NAME key=value ...
 // keys: CodeFacts fields (override the derived ones), LaunchFacts fields,
 // LaunchOptions fields (an OptInt by its name: set to the value), allow_ilv.
-// first_table=auto / tab2=auto: what decode_keys (decode.hip) gives the launch.
+// first_table=auto / tab2=auto: what decode_keys (api.hip) gives the launch.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>

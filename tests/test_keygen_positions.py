@@ -1,5 +1,5 @@
 """CPU check of the rule keygen_split_kernel uses for the error positions
-(decode.hip kg_resolve_wave): after the forward shuffle (introduce_errors,
+(keygen.hip kg_resolve_wave): after the forward shuffle (introduce_errors,
 qkd_ldpc_algorithm.cpp; std::shuffle's swap a[s] <-> a[x_s], x_s <= s), a[q] for
 q < ne is the last step s with x_s = q, and a position no step wrote after
 its own step follows the chain back through step q. Restated here in Python

@@ -1,5 +1,5 @@
 """Host model of the frame-syndrome kernel's butterfly bit transpose
-(decode_split.hip wave_transpose32 / transpose_stage): the stage list is read
+(frame_syn.hip wave_transpose32 / transpose_stage): the stage list is read
 from the HIP source, and the five stages -- partner lane l ^ s (ds_swizzle xor
 mode, within 32-lane halves), a rotate right by s (upper-block lanes) or
 32 - s (lower-block lanes) through v_alignbit_b32, and a v_bfi_b32 keeping the
@@ -10,7 +10,7 @@ import random
 import re
 
 SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                   "qkd_ldpc_amd", "csrc", "decode_split.hip")
+                   "qkd_ldpc_amd", "csrc", "frame_syn.hip")
 M32 = 0xFFFFFFFF
 
 

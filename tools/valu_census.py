@@ -63,7 +63,7 @@ def regions(src_path):
         "prologue": r"// ---- prologue\. Keys path",
         "iteration": r"// ---- iterations \(",
         "epilogue": r"// ---- outputs: SP_result",
-        "host": r"__global__ __launch_bounds__\(kSynBlock\) void frame_syn_kernel",
+        "host": r"// The instantiations of decode_split_kernel, by key",     # (the split_bucket lookup)
     }
     for name, p in pats.items():
         for i, l in enumerate(lines, 1):
