@@ -593,9 +593,9 @@ QKD_API size_t qkd_privacy_long_scratch_bytes(uint32_t n_in, uint32_t out_bits);
  * `device`, only byte & 1 counts; contiguous blocks, base address of any
  * alignment), Wo = ceil(out_bits / 64), packed as by qkd_privacy_amplify_batch.
  * keep[n_blocks] (may be NULL) is per BLOCK: a block with keep[b] == 0 gets Wo
- * zero words. A caller who wants only the verified frames of a block compacts
- * them into the block first; Alice must hash the same frames, so the block's
- * length has to be agreed with her. scratch: device memory of at least
+ * zero words. A caller who wants only the verified frames of a block calls
+ * qkd_privacy_amplify_kept_batch (below), which compacts them on the device
+ * at the block's fixed length. scratch: device memory of at least
  * qkd_privacy_long_scratch_bytes(n_in, out_bits) bytes, any alignment, any
  * contents; the blocks of a call run one after another through it, and the
  * key string's transform is taken once per call. out_words is fully
@@ -610,6 +610,68 @@ QKD_API qkd_status qkd_privacy_amplify_long_batch(int device, const uint8_t *key
                                                   const uint64_t *hash_words, const uint8_t *keep,
                                                   uint64_t *out_words, void *scratch, size_t scratch_bytes,
                                                   void *stream);
+
+/* ---- long-block privacy amplification of the kept frames of a block -----------
+ * The link between verification and the long form: a block is
+ * B = frames_per_block frames of N = frame_bits bits, keep[] holds one flag per
+ * FRAME (typically `verified` of qkd_reconcile_verify_batch), and only the kept
+ * frames are hashed, without the host ever reading a flag. With n_in = B * N,
+ * L = out_bits and Wo = ceil(L / 64):
+ *
+ * For block b let x_b be its kept frames set end to end in ascending frame
+ * order, followed by zeros up to n_in bits. out_words[b * Wo ..] is, word for
+ * word, what qkd_privacy_amplify_long_batch gives for x_b with n_in, L, the
+ * same key string (hash_words[Wp], Wp = qkd_privacy_long_key_words(n_in, L), or
+ * the same seed) and keep == NULL. kept[b] (may be NULL) is the number of kept
+ * frames of block b. So:
+ *   - a block with no kept frame gets Wo zero words;
+ *   - with every frame kept the call is qkd_privacy_amplify_long_batch on the
+ *     same buffer;
+ *   - the bytes of a dropped frame have no effect on any output;
+ *   - the PREFIX RULE: out_i = XOR_p r[p + i] x_p depends neither on the zeros
+ *     behind the input nor on out_bits, so for any L' <= min(L, kept[b] * N)
+ *     the first L' output bits of block b are
+ *     qkd_privacy_amplify_long_batch(the kept frames compacted,
+ *     n_in = kept[b] * N, out_bits = L') under the first
+ *     qkd_privacy_long_key_words(kept[b] * N, L') words of the same string, or
+ *     under the same seed.
+ * The caller's finite-key formula picks the final length l <= out_bits from
+ * kept[b] and takes the first l bits. Alice, who makes the same call on her
+ * frames, gets the same bits as long as both sides use the same keep flags
+ * (they are public), the same B and the same l.
+ *
+ * frames[n_blocks * B * N]: 0/1 bytes on `device`, only byte & 1 counts, any
+ * base alignment. keep[n_blocks * B]: required, device memory; a frame is kept
+ * when its byte is nonzero (any nonzero value). kept[n_blocks]: device memory
+ * or NULL. scratch: device memory of at least
+ * qkd_privacy_kept_scratch_bytes(N, B, L, n_blocks) bytes, any alignment, any
+ * contents. out_words and kept are fully overwritten, and nothing is written
+ * outside them and the scratch.
+ * QKD_ERR_INVALID_ARG, before any device work, for NULL frames, keep,
+ * out_words or scratch; n_blocks of 0; n_blocks * B >= 2^32; N < 1 or B < 1;
+ * B * N (taken in 64 bits) above QKD_PRIVACY_LONG_MAX_BITS; out_bits outside
+ * 1..B * N; B * N + out_bits - 1 > QKD_PRIVACY_LONG_MAX_BITS; scratch_bytes
+ * below qkd_privacy_kept_scratch_bytes; or a bad device. Kernel launches on the
+ * stream only (one scan of the flags per call, then per block an input stage
+ * that gathers the kept frames and the long form's passes): no allocation, no
+ * host copy, no synchronisation, no atomics (the same bits on every run);
+ * capturable in a graph, and a replay follows the flags' current contents. */
+
+/* The bytes of device scratch one call needs:
+ * qkd_privacy_long_scratch_bytes(B * N, out_bits), plus a frame list of
+ * n_blocks * B 32-bit entries, one byte per block, and 16 bytes of alignment
+ * slack. Unlike the long form's size it depends on n_blocks. 0 for sizes
+ * outside the range (B * N in 64 bits or out_bits outside the long form's,
+ * n_blocks of 0, n_blocks * B >= 2^32). Host only. */
+QKD_API size_t qkd_privacy_kept_scratch_bytes(uint32_t frame_bits, uint32_t frames_per_block,
+                                              uint32_t out_bits, size_t n_blocks);
+
+QKD_API qkd_status qkd_privacy_amplify_kept_batch(int device, const uint8_t *frames, size_t n_blocks,
+                                                  uint32_t frame_bits, uint32_t frames_per_block,
+                                                  uint32_t out_bits, uint64_t hash_seed,
+                                                  const uint64_t *hash_words, const uint8_t *keep,
+                                                  uint64_t *out_words, uint32_t *kept, void *scratch,
+                                                  size_t scratch_bytes, void *stream);
 
 /* generate_random_bit_array + introduce_errors (array_and_matrix_operations.cpp:424-460)
  * for frame k seeded with seeds[k] + seed_offset (simulation.cpp:163,247),

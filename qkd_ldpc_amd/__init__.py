@@ -15,6 +15,7 @@ src/array_and_matrix_operations.hpp) with batched, device-resident arrays:
   (no counterpart) key verification tags            verify_tags(H, bits, ...), reconcile(..., alice_tags=)
   (no counterpart) privacy amplification            privacy_amplify(keys, out_bits, ..., keep=verified)
   (no counterpart) ... of blocks up to 2^27 bits     privacy_amplify_long(keys, out_bits, ..., scratch=)
+  (no counterpart) ... of a block's verified frames  privacy_amplify_kept(frames, verified, out_bits, ...)
   (no counterpart) punctured / shortened frames     AdaptPlan, adapt_embed, adapt_extract,
                                                     reconcile_adaptive(H, plan, bob_payload, ...)
   (no counterpart) blind reconciliation             reconcile_blind(H, plan, bob_payload, ..., revealed=)
@@ -51,6 +52,7 @@ __all__ = [
     "verify_key_words", "verify_expand_key", "verify_tags",
     "privacy_key_words", "privacy_expand_key", "privacy_amplify",
     "privacy_long_key_words", "privacy_long_expand_key", "privacy_long_scratch_bytes", "privacy_amplify_long",
+    "privacy_kept_scratch_bytes", "privacy_amplify_kept",
     "AdaptPlan", "adapt_positions", "adapt_embed", "adapt_extract", "reconcile_adaptive",
     "reconcile_blind", "BlindResult",
 ]
@@ -834,7 +836,8 @@ def privacy_amplify_long(keys, out_bits: int, hash_seed: int = 0, hash_words=Non
     [B, ceil(out_bits / 64)] int64 bit patterns. hash_words holds
     privacy_long_key_words(n_in, out_bits) words; the seeded string is a computational
     stand-in. keep ([B] uint8) is per block: a block with 0 gets all-zero words (to hash only
-    the verified frames of a block, compact them first, to a length agreed with Alice).
+    the verified frames of a block, call privacy_amplify_kept, which compacts them on the
+    device at the block's fixed length).
     scratch: a uint8 device tensor of at least privacy_long_scratch_bytes(n_in, out_bits)
     bytes (about 8 bytes per bit of the power of two at or above n_in + out_bits - 1), to
     reuse one allocation over calls; without it the wrapper allocates one for the call."""
@@ -875,6 +878,76 @@ def privacy_long_scratch_bytes(n_in: int, out_bits: int) -> int:
     if not (0 <= n_in < 2**32 and 0 <= out_bits < 2**32):
         return 0
     return int(N.lib().qkd_privacy_long_scratch_bytes(n_in, out_bits))
+
+
+def privacy_kept_scratch_bytes(frame_bits: int, frames_per_block: int, out_bits: int, n_blocks: int = 1) -> int:
+    """The bytes of scratch privacy_amplify_kept needs (qkd_privacy_kept_scratch_bytes):
+    privacy_long_scratch_bytes(frames_per_block * frame_bits, out_bits) plus a frame list of
+    n_blocks * frames_per_block 32-bit entries, a byte per block and 16 bytes of slack, so
+    that, unlike the long form's, it grows with n_blocks; 0 for sizes outside the range."""
+    if not all(isinstance(v, int) and 0 <= v < 2**32 for v in (frame_bits, frames_per_block, out_bits)):
+        return 0
+    if not (isinstance(n_blocks, int) and 0 <= n_blocks < 2**64):
+        return 0
+    return int(N.lib().qkd_privacy_kept_scratch_bytes(frame_bits, frames_per_block, out_bits, n_blocks))
+
+
+def privacy_amplify_kept(frames, keep, out_bits: int, frames_per_block: int | None = None, hash_seed: int = 0,
+                         hash_words=None, scratch=None, stream=None):
+    """Long-block privacy amplification of the kept frames of each block
+    (qkd_privacy_amplify_kept_batch): frames [F, N] uint8 on the GPU (a key bit is
+    byte & 1), keep [F] uint8 (a frame is kept when its byte is nonzero; typically
+    ReconcileResult.verified), blocks of B = frames_per_block consecutive frames (default F:
+    one block; F % B != 0 is an error). Returns (out, kept): out [F // B, ceil(out_bits / 64)]
+    int64, the hash of privacy_amplify_long of each block's kept frames set end to end in
+    frame order with zeros behind them, at the fixed length n_in = B * N; kept [F // B] int32,
+    the kept frames of each block. A block that keeps nothing gets zero words, and a dropped
+    frame's bytes change nothing. The flags are read on the device only: no host copy, no
+    synchronisation, capturable in a graph.
+
+    The prefix rule: out_i = XOR_p r[p + i] x_p depends neither on the zeros behind the input
+    nor on out_bits, so for any l <= min(out_bits, kept * N) the first l bits of a block are
+    privacy_amplify_long(frames[keep != 0] as one block of kept * N bits, l) under the first
+    privacy_long_key_words(kept * N, l) words of the same string, or under the same seed. How
+    many bits to take is the caller's decision from kept (the finite-key formula); Alice, who
+    makes the same call on her frames with the same public flags, B and l, gets the same bits.
+
+    hash_words holds privacy_long_key_words(B * N, out_bits) words; the seeded string is a
+    computational stand-in. scratch: a uint8 device tensor of at least
+    privacy_kept_scratch_bytes(N, B, out_bits, F // B) bytes; without it the wrapper allocates
+    one for the call."""
+    _need_cuda(frames, torch.uint8, "frames")
+    if frames.dim() != 2 or frames.shape[0] < 1 or frames.shape[1] < 1:
+        raise QkdError(N.ERR_INVALID_ARG, f"frames must have shape [F, N], got {list(frames.shape)}")
+    f, n = int(frames.shape[0]), int(frames.shape[1])
+    b = f if frames_per_block is None else frames_per_block
+    if not isinstance(b, int) or b < 1 or f % b != 0:
+        raise QkdError(N.ERR_INVALID_ARG, f"frames_per_block must divide the {f} frames, got {b}")
+    n_in, blocks = b * n, f // b
+    if not isinstance(out_bits, int) or not 1 <= out_bits <= n_in:
+        raise QkdError(N.ERR_INVALID_ARG, f"out_bits must be in 1..{n_in}")
+    wp = privacy_long_key_words(n_in, out_bits)
+    if wp == 0:
+        raise QkdError(N.ERR_INVALID_ARG, "frames_per_block * N + out_bits - 1 exceeds 2^27 bits")
+    dev = _Device(frames.device.index)
+    _need_vec(keep, torch.uint8, f, "keep", dev)
+    if hash_words is not None:
+        _need_tags(hash_words, wp, "hash_words", dev)
+    need = privacy_kept_scratch_bytes(n, b, out_bits, blocks)
+    ts = _torch_stream(stream, dev.device)
+    if scratch is None:
+        # allocated under the launch stream, as in privacy_amplify_long
+        with torch.cuda.stream(ts):
+            scratch = torch.empty(need, dtype=torch.uint8, device=frames.device)
+    else:
+        _need_cuda(scratch, torch.uint8, "scratch", dev)
+    seed = (0 if hash_seed is None else int(hash_seed)) & (2**64 - 1)
+    out = torch.empty(blocks, (out_bits + 63) // 64, dtype=torch.int64, device=frames.device)
+    kept = torch.empty(blocks, dtype=torch.int32, device=frames.device)
+    N.check(N.lib().qkd_privacy_amplify_kept_batch(dev.device, _ptr(frames), blocks, n, b, out_bits, seed,
+                                                   _ptr(hash_words), _ptr(keep), _ptr(out), _ptr(kept), _ptr(scratch),
+                                                   scratch.numel(), int(ts.cuda_stream)))
+    return out, kept
 
 
 def keygen(H: HMatrix, seeds, q_nominal: float, seed_offset: int = 0, workspace=None,

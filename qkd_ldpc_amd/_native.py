@@ -71,6 +71,7 @@ EXPORTS = [
     "qkd_privacy_key_words", "qkd_privacy_expand_key", "qkd_privacy_amplify_batch",
     "qkd_privacy_long_key_words", "qkd_privacy_long_expand_key", "qkd_privacy_long_scratch_bytes",
     "qkd_privacy_amplify_long_batch",
+    "qkd_privacy_kept_scratch_bytes", "qkd_privacy_amplify_kept_batch",
     "qkd_adapt_create", "qkd_adapt_destroy", "qkd_adapt_get_info", "qkd_adapt_positions",
     "qkd_adapt_embed_batch", "qkd_adapt_extract_batch", "qkd_reconcile_adaptive_batch",
     "qkd_reconcile_blind_batch",
@@ -148,6 +149,8 @@ def lib():
             "qkd_privacy_long_expand_key": (st, [U64, U32, U32, P]),
             "qkd_privacy_long_scratch_bytes": (SZ, [U32, U32]),
             "qkd_privacy_amplify_long_batch": (st, [C.c_int, P, SZ, U32, U32, U64, P, P, P, P, SZ, P]),
+            "qkd_privacy_kept_scratch_bytes": (SZ, [U32, U32, U32, SZ]),
+            "qkd_privacy_amplify_kept_batch": (st, [C.c_int, P, SZ, U32, U32, U32, U64, P, P, P, P, P, SZ, P]),
             "qkd_adapt_create": (P, [P, P, I32, P, I32, C.POINTER(st)]),
             "qkd_adapt_destroy": (None, [P]),
             "qkd_adapt_get_info": (st, [P, C.POINTER(AdaptInfo)]),

@@ -32,6 +32,14 @@
 // computed once per call, with T^-1 folded in and in Montgomery form; the
 // blocks of a call then run one after another through the same T residues.
 //
+// qkd_privacy_amplify_kept_batch hashes only the kept frames of a block of B
+// frames, as if they stood compacted at its front with zeros behind them: one
+// scan per call turns the frame flags into a list of the kept frames of each
+// block (kept_scan_kernel), and the input stage reads position p of the
+// compacted block from frame list[p / N] (ntt_gather_x_kernel, the division by
+// a reciprocal from the host); every pass after the input stage is the long
+// form's, skipped through its keep byte for a block that keeps nothing.
+//
 // Plain loads, LDS and vector stores, launches on the caller's stream only:
 // no atomics, no allocation, no host copy, no synchronisation.
 #include <algorithm>
@@ -61,6 +69,7 @@ constexpr uint32_t kNttMaxLog2 = 13;         // S: residues of a workgroup in LD
 constexpr uint32_t kNttMinLog2 = 3;          // the debug option's lowest S
 constexpr uint32_t kNttMaxCols = 6;          // at most 2^6 columns (256 contiguous bytes a row)
 constexpr uint32_t kNttMaxPasses = 32;
+constexpr uint32_t kKeptScanGrid = 1024;     // workgroups of the kept-frames scan at most (each strides over blocks)
 
 // The twiddle table (scratch): w^e = hi[e >> q] * lo[e & (2^q - 1)], Montgomery form.
 struct NttTable {
@@ -102,6 +111,68 @@ __global__ __launch_bounds__(kNttBlock) void ntt_unpack_x_kernel(uint32_t* d, ui
     for (uint32_t j = 0; j < 4; ++j) {
         const uint32_t p = (T - (4u * g + j)) & (T - 1u);
         v[j] = p < n_in ? (uint32_t)(x[p] & 1) : 0u;
+    }
+    reinterpret_cast<uint4*>(d)[g] = make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+// The scan of qkd_privacy_amplify_kept_batch, one workgroup per block (a
+// workgroup takes the blocks blockIdx.x, blockIdx.x + gridDim.x, ...):
+// list[b B + rank] = the index in block b of its kept frame of that rank, in
+// ascending order (an exclusive prefix sum of keep != 0: a ballot and popcounts
+// inside a wave, the waves' counts through LDS, a running carry over the chunks
+// of kNttBlock frames), qkdn::kKeptNone for the ranks from the count up to B;
+// kept[b] (may be NULL) = the count, nonempty[b] = whether it is nonzero.
+__global__ __launch_bounds__(kNttBlock) void kept_scan_kernel(const uint8_t* keep, uint32_t n_blocks, uint32_t B,
+                                                             uint32_t* list, uint32_t* kept, uint8_t* nonempty) {
+    constexpr uint32_t kWaves = kNttBlock / 64u;
+    __shared__ uint32_t wave_count[kWaves];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (size_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {       // (64 bits: b + gridDim.x may pass 2^32)
+        const size_t row = b * B;
+        uint32_t carry = 0;                                        // kept frames of the chunks before (uniform)
+        for (uint32_t f0 = 0; f0 < B; f0 += kNttBlock) {
+            const uint32_t f = f0 + threadIdx.x;                   // (f0 < B <= 2^27: no wrap)
+            const bool on = f < B && keep[row + f] != 0;
+            const uint64_t m = __ballot(on);
+            if (lane == 0) wave_count[wave] = (uint32_t)__popcll(m);
+            __syncthreads();
+            uint32_t before = 0, total = 0;
+            for (uint32_t w = 0; w < kWaves; ++w) {
+                const uint32_t c = wave_count[w];
+                before += w < wave ? c : 0u;
+                total += c;
+            }
+            if (on) list[row + carry + before + (uint32_t)__popcll(m & (((uint64_t)1 << lane) - 1u))] = f;
+            carry += total;
+            __syncthreads();                                       // (wave_count is rewritten by the next chunk)
+        }
+        for (uint32_t r = carry + threadIdx.x; r < B; r += kNttBlock) list[row + r] = qkdn::kKeptNone;
+        if (threadIdx.x == 0) {
+            if (kept) kept[b] = carry;
+            nonempty[b] = carry ? 1 : 0;
+        }
+    }
+}
+
+// The input stage of qkd_privacy_amplify_kept_batch, ntt_unpack_x_kernel's
+// counterpart: d[(T - p) mod T] = bit p of the block's kept frames set end to
+// end, zero behind them, four residues to a lane. frames and list: the
+// block's; n = frame_bits, recip = qkdn::kept_reciprocal(n). Position p lies in
+// slot p / n, which holds frame list[slot] when that is a frame; a slot at or
+// past B (p >= B n) is past the block. Skipped, as every later pass, for a
+// block that keeps no frame.
+__global__ __launch_bounds__(kNttBlock) void ntt_gather_x_kernel(uint32_t* d, uint32_t T, const uint8_t* frames,
+                                                                uint32_t n, uint32_t recip, uint32_t B,
+                                                                const uint32_t* list, const uint8_t* nonempty) {
+    if (!*nonempty) return;
+    const uint32_t g = blockIdx.x * kNttBlock + threadIdx.x;
+    if (g >= T / 4u) return;
+    uint32_t slot[4], off[4], v[4];
+    qkdn::kept_lane_positions(T, g, n, recip, slot, off);
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t f = slot[j] < B ? list[slot[j]] : qkdn::kKeptNone;
+        v[j] = f < B ? (uint32_t)(frames[f * n + off[j]] & 1) : 0u;                    // (f n + off < B n <= 2^27)
     }
     reinterpret_cast<uint4*>(d)[g] = make_uint4(v[0], v[1], v[2], v[3]);
 }
@@ -280,6 +351,90 @@ uint32_t plan_passes(uint32_t k, uint32_t S, NttPass* strided, uint32_t* s_block
     return n;
 }
 
+// What a call's launches share: where the arrays lie in the scratch, the
+// passes of the transform and the launch shapes. For sizes the argument check
+// accepted; S from the debug option.
+struct LongCall {
+    uint32_t n_in, out_bits, k, T, wo, key_words;
+    uint32_t* x;             // the block's T residues
+    uint32_t* h;             // the key string's transform
+    uint32_t *lo, *hi;       // the twiddle table (tab reads it)
+    uint32_t* end;           // one past the table: where an entry's own tables may start
+    NttTable tab;
+    NttPass strided[kNttMaxPasses];
+    uint32_t n_strided, s_block;
+    dim3 lanes, grid4, grid_strided, grid_block;
+    hipStream_t st;
+};
+
+LongCall plan_call(void* scratch, uint32_t n_in, uint32_t out_bits, hipStream_t st) {
+    uint32_t S = kNttMaxLog2;
+    if (const DbgOpt cap = debug_option(nullptr, "QKD_PRIVACY_NTT_LOG2"))
+        S = (uint32_t)std::min<long>(std::max<long>(cap.as_long(), kNttMinLog2), kNttMaxLog2);
+    LongCall c;
+    c.n_in = n_in;
+    c.out_bits = out_bits;
+    c.k = qkdn::transform_log2(n_in, out_bits);
+    c.T = 1u << c.k;
+    const uint32_t q = qkdn::table_split_log2(c.k);
+    c.x = reinterpret_cast<uint32_t*>(((uintptr_t)scratch + 15u) & ~(uintptr_t)15u);
+    c.h = c.x + c.T;
+    c.lo = c.h + c.T;
+    c.hi = c.lo + (1u << q);
+    c.end = c.hi + (1u << (c.k - q));
+    c.tab = NttTable{c.lo, c.hi, q, c.k};
+    c.n_strided = plan_passes(c.k, S, c.strided, &c.s_block);
+    c.lanes = dim3(kNttBlock);
+    c.grid4 = dim3((c.T / 4u + kNttBlock - 1u) / kNttBlock);
+    c.grid_strided = dim3(c.T >> std::min(c.k, S));
+    c.grid_block = dim3(c.T >> c.s_block);
+    c.key_words = (uint32_t)qkdn::long_key_words(n_in, out_bits);
+    c.wo = (uint32_t)qkdv::privacy_out_words(out_bits);
+    c.st = st;
+    return c;
+}
+
+// once per call: the table and the key string's transform
+qkd_status launch_key_string(const LongCall& c, uint64_t hash_seed, const uint64_t* hash_words) {
+    const uint32_t w_form = qkdn::to_mont(qkdn::root_of_order_log2(c.k));
+    const uint32_t scale = qkdn::mont_mul(qkdn::to_mont(qkdn::inverse_of_length_log2(c.k)), qkdn::kR2);
+    hipLaunchKernelGGL(ntt_table_kernel, dim3(((1u << c.tab.q) + kNttBlock - 1u) / kNttBlock), c.lanes, 0, c.st,
+                       c.lo, c.hi, c.tab.q, c.k, w_form);
+    hipLaunchKernelGGL(ntt_unpack_key_kernel, c.grid4, c.lanes, 0, c.st, c.h, c.T, hash_seed, hash_words, c.key_words);
+    for (uint32_t i = 0; i < c.n_strided; ++i)
+        hipLaunchKernelGGL(ntt_strided_kernel<false>, c.grid_strided, c.lanes, 0, c.st, c.h, c.tab, c.strided[i],
+                           (const uint8_t*)nullptr);
+    hipLaunchKernelGGL(ntt_block_kernel<true>, c.grid_block, c.lanes, 0, c.st, c.h, (const uint32_t*)nullptr, c.tab,
+                       c.s_block, scale, (const uint8_t*)nullptr);
+    QKD_HIP(hipGetLastError());
+    return QKD_OK;
+}
+
+// One block, after its input stage has filled c.x: forward passes, the product
+// with the key string's transform inside the block pass, inverse passes, and
+// the packed output. kb: the block's keep byte (NULL: kept).
+qkd_status launch_block_passes(const LongCall& c, const uint8_t* kb, uint64_t* out) {
+    for (uint32_t i = 0; i < c.n_strided; ++i)
+        hipLaunchKernelGGL(ntt_strided_kernel<false>, c.grid_strided, c.lanes, 0, c.st, c.x, c.tab, c.strided[i], kb);
+    hipLaunchKernelGGL(ntt_block_kernel<false>, c.grid_block, c.lanes, 0, c.st, c.x, (const uint32_t*)c.h, c.tab,
+                       c.s_block, 0u, kb);
+    for (uint32_t i = c.n_strided; i-- > 0;)
+        hipLaunchKernelGGL(ntt_strided_kernel<true>, c.grid_strided, c.lanes, 0, c.st, c.x, c.tab, c.strided[i], kb);
+    hipLaunchKernelGGL(ntt_pack_kernel, dim3((64u * c.wo + kNttBlock - 1u) / kNttBlock), c.lanes, 0, c.st,
+                       (const uint32_t*)c.x, c.out_bits, c.wo, out, kb);
+    QKD_HIP(hipGetLastError());
+    return QKD_OK;
+}
+
+// The device of a call, checked as every entry checks it
+qkd_status check_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_error(QKD_ERR_DEVICE, "no HIP device available");
+    if (device < 0 || device >= ndev)
+        return set_error(QKD_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
+    return QKD_OK;
+}
+
 }  // namespace
 }  // namespace qkd
 
@@ -299,54 +454,47 @@ qkd_status qkd_privacy_amplify_long_batch(int device, const uint8_t* keys, size_
     if (const char* bad = qkda::privacy_amplify_long_args_error(keys, n_blocks, n_in, out_bits, out_words, scratch,
                                                                 scratch_bytes))
         return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_error(QKD_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev)
-        return set_error(QKD_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-    uint32_t S = kNttMaxLog2;
-    if (const DbgOpt cap = debug_option(nullptr, "QKD_PRIVACY_NTT_LOG2"))
-        S = (uint32_t)std::min<long>(std::max<long>(cap.as_long(), kNttMinLog2), kNttMaxLog2);
+    if (const qkd_status s = check_device(device)) return s;
     DeviceGuard g(device);
-    hipStream_t st = (hipStream_t)stream;
-
-    const uint32_t k = qkdn::transform_log2(n_in, out_bits), T = 1u << k, q = qkdn::table_split_log2(k);
-    uint32_t* x = reinterpret_cast<uint32_t*>(((uintptr_t)scratch + 15u) & ~(uintptr_t)15u);
-    uint32_t* h = x + T;
-    uint32_t* lo = h + T;
-    uint32_t* hi = lo + (1u << q);
-    const NttTable tab{lo, hi, q, k};
-    NttPass strided[kNttMaxPasses];
-    uint32_t s_block = 0;
-    const uint32_t n_strided = plan_passes(k, S, strided, &s_block);
-    const uint32_t w_form = qkdn::to_mont(qkdn::root_of_order_log2(k));
-    const uint32_t scale = qkdn::mont_mul(qkdn::to_mont(qkdn::inverse_of_length_log2(k)), qkdn::kR2);
-    const dim3 lanes(kNttBlock);
-    const dim3 grid4((T / 4u + kNttBlock - 1u) / kNttBlock), grid_strided(T >> std::min(k, S)), grid_block(T >> s_block);
-    const uint32_t key_words = (uint32_t)qkdn::long_key_words(n_in, out_bits);
-    const uint32_t wo = (uint32_t)qkdv::privacy_out_words(out_bits);
-
-    // once per call: the table and the key string's transform
-    hipLaunchKernelGGL(ntt_table_kernel, dim3(((1u << q) + kNttBlock - 1u) / kNttBlock), lanes, 0, st, lo, hi, q, k,
-                       w_form);
-    hipLaunchKernelGGL(ntt_unpack_key_kernel, grid4, lanes, 0, st, h, T, hash_seed, hash_words, key_words);
-    for (uint32_t i = 0; i < n_strided; ++i)
-        hipLaunchKernelGGL(ntt_strided_kernel<false>, grid_strided, lanes, 0, st, h, tab, strided[i],
-                           (const uint8_t*)nullptr);
-    hipLaunchKernelGGL(ntt_block_kernel<true>, grid_block, lanes, 0, st, h, (const uint32_t*)nullptr, tab, s_block,
-                       scale, (const uint8_t*)nullptr);
-    QKD_HIP(hipGetLastError());
-
+    const LongCall c = plan_call(scratch, n_in, out_bits, (hipStream_t)stream);
+    if (const qkd_status s = launch_key_string(c, hash_seed, hash_words)) return s;
     for (size_t b = 0; b < n_blocks; ++b) {
         const uint8_t* kb = keep ? keep + b : nullptr;
-        hipLaunchKernelGGL(ntt_unpack_x_kernel, grid4, lanes, 0, st, x, T, keys + b * (size_t)n_in, n_in, kb);
-        for (uint32_t i = 0; i < n_strided; ++i)
-            hipLaunchKernelGGL(ntt_strided_kernel<false>, grid_strided, lanes, 0, st, x, tab, strided[i], kb);
-        hipLaunchKernelGGL(ntt_block_kernel<false>, grid_block, lanes, 0, st, x, (const uint32_t*)h, tab, s_block, 0u, kb);
-        for (uint32_t i = n_strided; i-- > 0;)
-            hipLaunchKernelGGL(ntt_strided_kernel<true>, grid_strided, lanes, 0, st, x, tab, strided[i], kb);
-        hipLaunchKernelGGL(ntt_pack_kernel, dim3((64u * wo + kNttBlock - 1u) / kNttBlock), lanes, 0, st,
-                           (const uint32_t*)x, out_bits, wo, out_words + b * (size_t)wo, kb);
-        QKD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ntt_unpack_x_kernel, c.grid4, c.lanes, 0, c.st, c.x, c.T, keys + b * (size_t)n_in, n_in, kb);
+        if (const qkd_status s = launch_block_passes(c, kb, out_words + b * (size_t)c.wo)) return s;
+    }
+    return QKD_OK;
+}
+
+size_t qkd_privacy_kept_scratch_bytes(uint32_t frame_bits, uint32_t frames_per_block, uint32_t out_bits,
+                                      size_t n_blocks) {
+    return qkdn::kept_scratch_bytes(frame_bits, frames_per_block, out_bits, n_blocks);
+}
+
+qkd_status qkd_privacy_amplify_kept_batch(int device, const uint8_t* frames, size_t n_blocks, uint32_t frame_bits,
+                                          uint32_t frames_per_block, uint32_t out_bits, uint64_t hash_seed,
+                                          const uint64_t* hash_words, const uint8_t* keep, uint64_t* out_words,
+                                          uint32_t* kept, void* scratch, size_t scratch_bytes, void* stream) {
+    clear_error();
+    if (const char* bad = qkda::privacy_amplify_kept_args_error(frames, n_blocks, frame_bits, frames_per_block,
+                                                                out_bits, keep, out_words, scratch, scratch_bytes))
+        return set_error(QKD_ERR_INVALID_ARG, "%s", bad);
+    if (const qkd_status s = check_device(device)) return s;
+    DeviceGuard g(device);
+    const uint32_t n_in = frame_bits * frames_per_block;                 // (checked: at most 2^27)
+    const LongCall c = plan_call(scratch, n_in, out_bits, (hipStream_t)stream);
+    // this entry's tables, behind the long form's: the frame list on a 16-byte boundary, then a byte per block
+    uint32_t* list = reinterpret_cast<uint32_t*>(((uintptr_t)c.end + 15u) & ~(uintptr_t)15u);
+    uint8_t* nonempty = reinterpret_cast<uint8_t*>(list + n_blocks * frames_per_block);
+    hipLaunchKernelGGL(kept_scan_kernel, dim3((uint32_t)std::min<size_t>(n_blocks, kKeptScanGrid)), c.lanes, 0, c.st,
+                       keep, (uint32_t)n_blocks, frames_per_block, list, kept, nonempty);
+    if (const qkd_status s = launch_key_string(c, hash_seed, hash_words)) return s;
+    const uint32_t recip = qkdn::kept_reciprocal(frame_bits);
+    for (size_t b = 0; b < n_blocks; ++b) {
+        hipLaunchKernelGGL(ntt_gather_x_kernel, c.grid4, c.lanes, 0, c.st, c.x, c.T, frames + b * (size_t)n_in,
+                           frame_bits, recip, frames_per_block, (const uint32_t*)(list + b * (size_t)frames_per_block),
+                           (const uint8_t*)(nonempty + b));
+        if (const qkd_status s = launch_block_passes(c, nonempty + b, out_words + b * (size_t)c.wo)) return s;
     }
     return QKD_OK;
 }

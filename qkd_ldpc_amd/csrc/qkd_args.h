@@ -2,7 +2,8 @@
 // HIP so that a stand-alone host program can exercise them
 // (tests/native/reconcile_args_check.cpp, tests/native/verify_hash_check.cpp,
 // tests/native/privacy_hash_check.cpp, tests/native/blind_args_check.cpp,
-// tests/native/adapt_verify_args_check.cpp, tests/native/ntt_mod_check.cpp).
+// tests/native/adapt_verify_args_check.cpp, tests/native/ntt_mod_check.cpp,
+// tests/native/privacy_kept_check.cpp).
 #pragma once
 
 #include <stddef.h>
@@ -124,6 +125,29 @@ inline const char* privacy_amplify_long_args_error(const uint8_t* keys, size_t n
     if (qkdn::long_key_words(n_in, out_bits) == 0) return "n_in + out_bits - 1 exceeds QKD_PRIVACY_LONG_MAX_BITS";
     if (scratch_bytes < qkdn::long_scratch_bytes(n_in, out_bits))
         return "scratch_bytes is below qkd_privacy_long_scratch_bytes(n_in, out_bits)";
+    return nullptr;
+}
+
+// qkd_privacy_amplify_kept_batch's arguments, the same way: a block of
+// frames_per_block frames of frame_bits bits in the long form's n_in (their
+// product taken in 64 bits), the frame flags, and this entry's own scratch
+// size. hash_words and kept may be NULL and are not looked at.
+inline const char* privacy_amplify_kept_args_error(const uint8_t* frames, size_t n_blocks, uint32_t frame_bits,
+                                                   uint32_t frames_per_block, uint32_t out_bits, const uint8_t* keep,
+                                                   const uint64_t* out_words, const void* scratch,
+                                                   size_t scratch_bytes) {
+    if (!frames || !keep || !out_words || !scratch) return "null argument";
+    if (n_blocks == 0) return "n_blocks must be > 0";
+    if (frame_bits < 1 || frames_per_block < 1) return "frame_bits and frames_per_block must be >= 1";
+    if (n_blocks > 0xffffffffull || (uint64_t)n_blocks * frames_per_block > 0xffffffffull)
+        return "n_blocks * frames_per_block must be below 2^32";
+    const uint64_t n_in = (uint64_t)frame_bits * frames_per_block;
+    if (n_in > qkdn::kLongMaxBits) return "frame_bits * frames_per_block must be in 1..QKD_PRIVACY_LONG_MAX_BITS";
+    if (out_bits < 1 || out_bits > n_in) return "out_bits must be in 1..frame_bits * frames_per_block";
+    if (qkdn::long_key_words((uint32_t)n_in, out_bits) == 0)
+        return "frame_bits * frames_per_block + out_bits - 1 exceeds QKD_PRIVACY_LONG_MAX_BITS";
+    if (scratch_bytes < qkdn::kept_scratch_bytes(frame_bits, frames_per_block, out_bits, n_blocks))
+        return "scratch_bytes is below qkd_privacy_kept_scratch_bytes(frame_bits, frames_per_block, out_bits, n_blocks)";
     return nullptr;
 }
 

@@ -1,7 +1,9 @@
 // qkd_ntt.h — the modular arithmetic of the long-block privacy amplification
 // (qkd_privacy_amplify_long_batch, privacy_ntt.hip), shared by the kernels,
 // the host helpers qkd_privacy_long_* and a stand-alone host program
-// (tests/native/ntt_mod_check.cpp). Plain C++ for the host (no HIP headers
+// (tests/native/ntt_mod_check.cpp), and the index arithmetic of its
+// kept-frames form (qkd_privacy_amplify_kept_batch;
+// tests/native/privacy_kept_check.cpp). Plain C++ for the host (no HIP headers
 // needed), __host__ __device__ under hipcc.
 //
 // The hash is qkd_privacy.h's: out_k = XOR over p with x_p = 1 of r[p + k].
@@ -114,6 +116,101 @@ inline size_t long_scratch_bytes(uint32_t n_in, uint32_t out_bits) {
     if (long_key_words(n_in, out_bits) == 0) return 0;
     const uint32_t k = transform_log2(n_in, out_bits), q = table_split_log2(k);
     return 4u * (((size_t)2 << k) + ((size_t)1 << q) + ((size_t)1 << (k - q))) + 16u;
+}
+
+// ---- the kept-frames form (qkd_privacy_amplify_kept_batch) ---------------------
+// A block is B frames of N bits; the kept ones, in ascending order, are hashed
+// as if they stood at the front of the block with zeros behind them. A scan
+// writes list[rank] = the index in the block of the kept frame of that rank,
+// and kKeptNone for the ranks from the kept count up to B; the input stage then
+// reads position p of the compacted block from frame list[p / N] at bit p % N.
+
+constexpr uint32_t kKeptNone = 0xffffffffu;    // list entry of a rank no kept frame has
+
+// The scratch of qkd_privacy_amplify_kept_batch in bytes: the long form's for a
+// block of B N bits, the frame list (n_blocks B 32-bit entries), one byte per
+// block (nonzero when the block keeps a frame), and 16 bytes to start the list
+// on a 16-byte boundary. 0 for sizes outside the range: B N in 64 bits not a
+// long-form n_in for out_bits, no block, or n_blocks B at or above 2^32.
+inline size_t kept_scratch_bytes(uint32_t frame_bits, uint32_t frames_per_block, uint32_t out_bits, size_t n_blocks) {
+    const uint64_t n_in = (uint64_t)frame_bits * frames_per_block;
+    if (n_in < 1 || n_in > kLongMaxBits) return 0;
+    if (n_blocks < 1 || n_blocks > 0xffffffffull || (uint64_t)n_blocks * frames_per_block > 0xffffffffull) return 0;
+    const size_t base = long_scratch_bytes((uint32_t)n_in, out_bits);
+    if (base == 0) return 0;
+    return base + 4u * (size_t)((uint64_t)n_blocks * frames_per_block) + n_blocks + 16u;
+}
+
+// floor(2^32 / n), n >= 1, held to 32 bits (2^32 - 1 for n = 1): the
+// reciprocal kept_divmod multiplies by, computed once per call on the host
+QKD_VHD uint32_t kept_reciprocal(uint32_t n) {
+    const uint64_t m = ((uint64_t)1 << 32) / n;
+    return m > 0xffffffffull ? 0xffffffffu : (uint32_t)m;
+}
+
+// *q = p / n, *r = p % n for any 32-bit p, by a multiply-high with
+// recip = kept_reciprocal(n) and one correction: recip n = 2^32 - d with
+// 0 <= d < n (d = 1 for n = 1), so p / n - p recip / 2^32 = p d / (n 2^32) < 1
+// and the estimate is the quotient or one below it.
+QKD_VHD void kept_divmod(uint32_t p, uint32_t n, uint32_t recip, uint32_t* q, uint32_t* r) {
+    uint32_t qe = (uint32_t)(((uint64_t)p * recip) >> 32);
+    uint32_t re = p - qe * n;
+    if (re >= n) {
+        ++qe;
+        re -= n;
+    }
+    *q = qe;
+    *r = re;
+}
+
+// The positions of the four residues a lane of the input stage owns, residue
+// i = 4 g + j holding position p_j = (T - i) mod T (x reversed cyclically), as
+// slot[j] = p_j / n and off[j] = p_j % n. T = 2^k >= 64, g < T / 4. One
+// division, for p_1 = T - 4 g - 1 (never wraps: 3 <= p_1 < T); p_2 and p_3 lie
+// one and two below it, p_0 one above it, or is 0 where g = 0, and a step of
+// one position crosses at most one frame boundary.
+QKD_VHD void kept_lane_positions(uint32_t T, uint32_t g, uint32_t n, uint32_t recip, uint32_t slot[4],
+                                 uint32_t off[4]) {
+    kept_divmod(T - 4u * g - 1u, n, recip, &slot[1], &off[1]);
+    for (uint32_t j = 2; j < 4; ++j) {
+        const bool wrap = off[j - 1u] == 0;
+        slot[j] = slot[j - 1u] - (wrap ? 1u : 0u);
+        off[j] = wrap ? n - 1u : off[j - 1u] - 1u;
+    }
+    if (g == 0) {
+        slot[0] = 0;
+        off[0] = 0;
+    } else {
+        const bool wrap = off[1] + 1u == n;
+        slot[0] = slot[1] + (wrap ? 1u : 0u);
+        off[0] = wrap ? 0u : off[1] + 1u;
+    }
+}
+
+// Host restatement of the scan kernel: list[0 .. B) and the kept count of one
+// block from its B flag bytes (a frame is kept when its byte is nonzero)
+inline uint32_t kept_scan_ref(const uint8_t* keep, uint32_t frames_per_block, uint32_t* list) {
+    uint32_t kept = 0;
+    for (uint32_t f = 0; f < frames_per_block; ++f)
+        if (keep[f]) list[kept++] = f;
+    for (uint32_t r = kept; r < frames_per_block; ++r) list[r] = kKeptNone;
+    return kept;
+}
+
+// Host restatement of the gathering input stage: the T residues of one block,
+// d[i] = the bit at position (T - i) mod T of the compacted block, through the
+// same index arithmetic as the kernel
+inline void kept_gather_ref(uint32_t* d, uint32_t T, const uint8_t* frames, uint32_t frame_bits,
+                            uint32_t frames_per_block, const uint32_t* list) {
+    const uint32_t recip = kept_reciprocal(frame_bits);
+    for (uint32_t g = 0; g < T / 4u; ++g) {
+        uint32_t slot[4], off[4];
+        kept_lane_positions(T, g, frame_bits, recip, slot, off);
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t f = slot[j] < frames_per_block ? list[slot[j]] : kKeptNone;
+            d[4u * g + j] = f < frames_per_block ? (uint32_t)(frames[(size_t)f * frame_bits + off[j]] & 1) : 0u;
+        }
+    }
 }
 
 // In-place transform of length 2^k, decimation in frequency: natural order
