@@ -66,11 +66,14 @@ CODE_SPECS = {
 }
 SMALL = ["r8", "i8", "i16", "i32", "i64", "dv5", "dv2"]
 FRAMES = {"i32": 8, "i64": 8, "i64g": 4, "i32l": 8, "i16l": 8, "i16g": 8, "n20544": 8, "n20480": 8, "n13056": 8}
+# every code code() and frames() know by name: this module's, and those a module that
+# shares the helpers adds (tests/test_sp64_kernels.py; frame counts: FRAMES)
+ALL_SPECS = dict(CODE_SPECS)
 
 
 @functools.lru_cache(maxsize=None)
 def code(name):
-    seed, dv, dc = CODE_SPECS[name]
+    seed, dv, dc = ALL_SPECS[name]
     return _socket_code(seed, dv, dc)
 
 
